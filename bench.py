@@ -22,6 +22,9 @@ up on some rank, all ranks agree (one all-reduce) to hand the targets over throu
 ring - and the line's `exchange` says so with every rank's error; TZ_BENCH_EXCHANGE=native makes that an exit code 4 too.
 
 Prints ONE JSON line (rank 0).  `value` = MCTS simulations/s summed over all ranks.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed step handed back (dump_outputs / step_outputs)
+as DIR/<name>.npy, so that two builds can be compared output for output on the same seeded inputs.
 """
 import argparse
 import ctypes as C
@@ -222,6 +225,61 @@ def precision_report(A, SP, W, args, primary_sims_per_s, moves=2):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+STATE_FIELDS = ("colors", "height", "top", "stones", "caps", "to_move", "n", "half_komi", "ply", "reversible_plies")
+
+
+def state_rows(states):
+    """STATE_DTYPE records -> one float64 row per position (every field; the colour bitmasks stay below 2^53, so exact)."""
+    cols = [states[f].astype(np.float64) for f in STATE_FIELDS]
+    return np.concatenate([c if c.ndim == 2 else c[:, None] for c in cols], axis=1)
+
+
+def eval_values(A, tags, bits):
+    """Eval (tag, bits) arrays -> their f32 values (impl From<Eval> for f32); proven results are few and go one by one."""
+    out = np.ascontiguousarray(bits, np.uint32).view(np.float32).copy()
+    for i in np.flatnonzero(tags != A.EVAL_VALUE):
+        out.flat[i] = A.eval_to_f32(tags.flat[i], bits.flat[i])
+    return out
+
+
+def step_outputs(A, mcts, last):
+    """What one self-play step hands back: the positions after the move, the statistics of the reused subtrees' roots and
+    their children (what the next move's search starts from), and the targets of the games that step finished (`last`:
+    the step's target lines from the native driver, or its target tuples from the Python one)."""
+    from takzero_amd import formats as F
+
+    targets = last["targets"] if "targets" in last else F.parse_targets(last["lines"], N_BOARD, HALF_KOMI)[0]
+    info, ch = mcts.root_info(), mcts.root_children()
+    states, moves, policy, _nmoves, value, ube = F.columns(targets, N_BOARD)
+    return {"positions": state_rows(mcts.get_positions()),
+            "root_visit_count": info["visit_count"], "root_n_children": info["n_children"],
+            "root_value": eval_values(A, info["eval_tag"], info["eval_bits"]), "root_std_dev": info["std_dev"],
+            "child_move_idx": ch["move_idx"], "child_visits": ch["visits"], "child_value": eval_values(A, ch["eval_tag"], ch["eval_bits"]),
+            "child_logit": ch["logit"], "child_prob": ch["prob"], "child_std_dev": ch["std_dev"],
+            "target_state": state_rows(states), "target_moves": moves, "target_policy": policy, "target_value": value,
+            "target_ube": ube}
+
+
+def dump_outputs(directory, arrays, limit=DUMP_LIMIT_BYTES):
+    """Writes every array as directory/<name>.npy: float32 stays float32, everything else becomes float64 (exact for the
+    integers here).  If the files would exceed `limit` bytes together, every array keeps the same share of its rows, a
+    fixed sample (seed 0), and <name>_rows.npy lists which rows were kept."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v if v.dtype == np.float32 else v.astype(np.float64) for k, v in arrays.items()}
+    budget = limit - 1024 * (2 * len(arrays) + 1)      # .npy headers
+    sample = sum(a.nbytes for a in arrays.values()) > budget
+    need = sum(a.nbytes + 8 * len(a) for a in arrays.values())
+    for name, a in arrays.items():
+        if sample and len(a) > 1:
+            keep = max(1, int(len(a) * budget / need))
+            rows = np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))
+            np.save(os.path.join(directory, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -246,6 +304,8 @@ def main():
                          "product: 2.4e-5, ~3x); bf16 = the f16 kernels 5 %% faster at 1e-3 .. 7e-3 (random-init scale)")
     ap.add_argument("--no-precision-report", action="store_true",
                     help="skip the second measurement (N = 1 only): throughput of the other precision and the measured logit errors")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     args = ap.parse_args()
     if args.sims is None:
         args.sims = 768 if args.search == "gumbel" else SIMS
@@ -350,6 +410,8 @@ def main():
         if dist is not None:
             dist.barrier()
 
+    last = {"lines": b""}                    # what the latest move handed back, for --dump-outputs
+
     def one_move():
         """One outer-loop iteration + the exchange of the finished targets (every rank ends up with all of them)."""
         if args.driver == "native":
@@ -360,9 +422,11 @@ def main():
             sp.take_text(1)
             if dist is not None and comm is None:
                 lines = SP.all_gather_bytes(lines, dev)
+            last["lines"] = lines
             return lines.count(b"\n")
         t, _r = sp.play_move()
-        return len(SP.all_gather_targets(t, N_BOARD, dev) if dist is not None else t)
+        last["targets"] = SP.all_gather_targets(t, N_BOARD, dev) if dist is not None else t
+        return len(last["targets"])
 
     gathered = 0
     for _ in range(args.warmup):
@@ -377,6 +441,8 @@ def main():
     dt = time.perf_counter() - t0
     sims1, evals1 = mcts.counters()
     prof = mcts.profile(reset=2)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(A, mcts, last))
 
     local = np.array([dt, sims1 - sims0, evals1 - evals0, args.games * args.steps], dtype=np.float64)
     if dist is not None:

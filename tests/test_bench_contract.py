@@ -36,6 +36,50 @@ def test_bench_line_has_the_contract_fields(extra):
 
 
 @pytest.mark.gpu
+def test_dumped_outputs_are_the_same_from_run_to_run(tmp_path):
+    """--dump-outputs DIR: what the last timed step computed, as float32 / float64 .npy files; the same arguments give the
+    same inputs, so two runs write the same arrays."""
+    import numpy as np
+
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("run%d" % run)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "1", "--games", "256",
+               "--sims", "16", "--no-cpu-baseline", "--no-precision-report", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])["steps"] == 6
+        dumps.append({p.stem: np.load(p) for p in d.glob("*.npy")})
+    a, b = dumps
+    assert sorted(a) == sorted(b) and {"positions", "root_visit_count", "child_visits", "child_logit", "target_policy"} <= set(a)
+    assert sum(os.path.getsize(p) for p in (tmp_path / "run0").glob("*.npy")) <= 64 << 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64), k
+        assert np.array_equal(a[k], b[k], equal_nan=True), k
+    assert a["root_visit_count"].shape == (256,) and a["positions"].shape[0] == 256 and a["child_visits"].sum() > 0
+
+
+def test_dump_outputs_keeps_a_fixed_sample_under_the_limit(tmp_path):
+    import numpy as np
+
+    import bench
+
+    arrays = {"small": np.arange(10, dtype=np.uint16), "big": np.arange(400_000, dtype=np.float32).reshape(4000, 100),
+              "wide": np.ones((4000, 50), np.uint32)}
+    for run in range(2):
+        bench.dump_outputs(str(tmp_path / str(run)), arrays, limit=1 << 20)
+    files = sorted(p.name for p in (tmp_path / "0").glob("*.npy"))
+    assert files == ["big.npy", "big_rows.npy", "small.npy", "small_rows.npy", "wide.npy", "wide_rows.npy"]
+    assert sum(os.path.getsize(p) for p in (tmp_path / "0").glob("*.npy")) <= 1 << 20
+    big, rows = np.load(tmp_path / "0" / "big.npy"), np.load(tmp_path / "0" / "big_rows.npy")
+    assert big.dtype == np.float32 and np.load(tmp_path / "0" / "wide.npy").dtype == np.float64
+    assert np.array_equal(big, arrays["big"][rows.astype(np.int64)]) and np.all(np.diff(rows) > 0)
+    assert all(np.array_equal(np.load(tmp_path / "0" / f), np.load(tmp_path / "1" / f)) for f in files)
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    assert np.array_equal(np.load(tmp_path / "whole" / "wide.npy"), arrays["wide"]) and not (tmp_path / "whole" / "wide_rows.npy").exists()
+
+
+@pytest.mark.gpu
 def test_two_rank_launch_as_the_driver_does_it():
     """python -m torch.distributed.run --nproc-per-node 2 bench.py --gpus 2 ...: both ranks on this box's one GPU with
     the target exchange over gloo (TZ_BENCH_BACKEND / TZ_BENCH_DEVICE are the rehearsal switches; on the 8-GPU node the
