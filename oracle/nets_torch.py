@@ -48,18 +48,51 @@ def forward(w, planes, blocks):
         return policy, torch.tanh(heads[0]), heads[1]
 
 
-def rnd(w, planes):
-    """normalized_rnd, net5.rs:193-211."""
+def rnd_raw(w, planes, dtype=torch.float32):
+    """forward_rnd (net5.rs:193-204) in `dtype` throughout: the squared distance of the two RND MLPs' outputs, [B]."""
     x = torch.from_numpy(planes) if isinstance(planes, np.ndarray) else planes
     with torch.no_grad():
-        x = x.reshape(x.shape[0], -1)
+        x = x.reshape(x.shape[0], -1).to(dtype)
         x = x / x.square().sum(dim=1, keepdim=True)
         outs = []
         for net in ("rnd_learning", "rnd_target"):
-            h = F.relu(F.linear(x, _t(w, net + ".input_linear.weight"), _t(w, net + ".input_linear.bias")))
-            h = F.relu(F.linear(h, _t(w, net + ".hidden_linear.weight"), _t(w, net + ".hidden_linear.bias")))
-            outs.append(F.linear(h, _t(w, net + ".final_linear.weight"), _t(w, net + ".final_linear.bias")))
-        raw = (outs[0] - outs[1]).square().sum(dim=1)
+            p = lambda layer, part: _t(w, "%s.%s.%s" % (net, layer, part)).to(dtype)
+            h = F.relu(F.linear(x, p("input_linear", "weight"), p("input_linear", "bias")))
+            h = F.relu(F.linear(h, p("hidden_linear", "weight"), p("hidden_linear", "bias")))
+            outs.append(F.linear(h, p("final_linear", "weight"), p("final_linear", "bias")))
+        return (outs[0] - outs[1]).square().sum(dim=1)
+
+
+def rnd_raw_storage(w, planes, storage):
+    """rnd_raw of the 16-bit MFMA path (storage torch.float16 or torch.bfloat16), rounded where the kernels store and exact
+    (fp64) in between: x / sum(x^2) computed in fp32 and stored (rnd_prep_state_kernel, the fused kernels' RND-input write); the
+    weights as build_layer converts them (round to nearest even); h1 and h2 as the linear layers' epilogue writes them (fp32
+    accumulator + bias, ReLU, converted); the final layer's output kept in fp32 (out_f32).  The distance is summed in fp64."""
+    x = torch.from_numpy(planes) if isinstance(planes, np.ndarray) else planes
+    st = lambda t: t.to(torch.float32).to(storage).to(torch.float64)
+    with torch.no_grad():
+        x = x.reshape(x.shape[0], -1).to(torch.float32)
+        x = st(x / x.square().sum(dim=1, keepdim=True))
+        outs = []
+        for net in ("rnd_learning", "rnd_target"):
+            wt = lambda layer: st(_t(w, "%s.%s.weight" % (net, layer)))
+            b = lambda layer: _t(w, "%s.%s.bias" % (net, layer)).to(torch.float64)
+            h = st(F.relu(F.linear(x, wt("input_linear"), b("input_linear"))))
+            h = st(F.relu(F.linear(h, wt("hidden_linear"), b("hidden_linear"))))
+            outs.append(F.linear(h, wt("final_linear"), b("final_linear")).to(torch.float32).to(torch.float64))
+        return (outs[0] - outs[1]).square().sum(dim=1)
+
+
+def rnd_calibrate(w, early, late):
+    """update_rnd (learn/src/rnd_normalization.rs:74-78) in fp64: min of rnd_raw over the early reference positions, max over
+    the late ones; returns (min, max) as Python floats."""
+    return float(rnd_raw(w, early, torch.float64).min()), float(rnd_raw(w, late, torch.float64).max())
+
+
+def rnd(w, planes):
+    """normalized_rnd, net5.rs:193-211."""
+    with torch.no_grad():
+        raw = rnd_raw(w, planes)
         mn, mx = _t(w, "min"), _t(w, "max")
         return ((raw - mn) / (mx - mn)).clamp(0.0, 1.0) * MAXIMUM_VARIANCE
 

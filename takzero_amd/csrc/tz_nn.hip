@@ -2610,14 +2610,26 @@ __global__ __launch_bounds__(64) void rnd_prep_state_kernel(const tz_state* stat
     const int in_size = NN * cin;
     constexpr int PER = (NN * 40 + 63) / 64;  // cin <= 40
     float x[PER];
-    float ss = 0.f;
 #pragma unroll
     for (int k = 0; k < PER; k++) {
         const int i = l + k * 64;
         x[k] = i < in_size ? plane_value<NB>(s, i / cin, i % cin, fd) : 0.f;
-        ss += x[k] * x[k];
     }
-    for (int d = 32; d >= 1; d >>= 1) ss += __shfl_xor(ss, d);
+    // sum(x^2) in the fused kernels' order - each square's planes in plane order, then the squares in order - so that x / sum(x^2)
+    // has the same bits as the input net_mfma_kernel / net_c6_kernel write (another order changes the sum's last bits, and now and
+    // then a stored element)
+    __shared__ float part[NN];
+    if (l < NN) {
+        float q = 0.f;
+        for (int c = 0; c < cin; c++) {
+            const float pv = plane_value<NB>(s, l, c, fd);
+            q += pv * pv;
+        }
+        part[l] = q;
+    }
+    __syncthreads();
+    float ss = 0.f;
+    for (int sq = 0; sq < NN; sq++) ss += part[sq];
 #pragma unroll
     for (int k = 0; k < PER; k++) {
         const int i = l + k * 64;

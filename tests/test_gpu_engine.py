@@ -24,16 +24,27 @@ def _agent_over(net):
 
 
 # (100,...) small nets; (5,...) full net5 = config 2 at test size; (4,...) config 1: 4x4, 64 games, 100 sims/move,
-# net4_simhash; (6,...) config 4 at test size: 6x6, net6_simhash
-@pytest.mark.parametrize("arch,n,blocks,prec,B,sims,moves", [(100, 5, 2, 0, 24, 30, 5), (100, 4, 1, 1, 16, 25, 4),
-                                                             (5, 5, 20, 0, 12, 24, 3), (5, 5, 20, 2, 12, 24, 2), (4, 4, 16, 0, 64, 100, 2),
-                                                             (6, 6, 16, 0, 8, 40, 2)])
-def test_engine_matches_oracle_search_with_same_net(oracle, arch, n, blocks, prec, B, sims, moves):
+# net4_simhash; (6,...) config 4 at test size: 6x6, net6_simhash.  rnd "calibrated": net5 with the RND min / max of update_rnd and a
+# constant UBE (test_gpu_uncertainty.rnd_fixture), so that the std_dev compared bit for bit carries a variance that depends on the
+# position (under min 0 / max 1 it is 1.56-1.57 everywhere)
+ENGINE_CASES = [(100, 5, 2, 0, 24, 30, 5, None), (100, 4, 1, 1, 16, 25, 4, None), (5, 5, 20, 0, 12, 24, 3, None),
+                (5, 5, 20, 2, 12, 24, 2, None), (4, 4, 16, 0, 64, 100, 2, None), (6, 6, 16, 0, 8, 40, 2, None),
+                (5, 5, 20, 2, 12, 24, 2, "calibrated")]
+
+
+@pytest.mark.parametrize("arch,n,blocks,prec,B,sims,moves,rnd", ENGINE_CASES,
+                         ids=["-".join(str(v) for v in case if v is not None) for case in ENGINE_CASES])
+def test_engine_matches_oracle_search_with_same_net(oracle, arch, n, blocks, prec, B, sims, moves, rnd):
     A = require_gpu()
     from takzero_amd import weights as W
 
     net = A.Net(arch=arch, n=n, precision=prec, blocks=blocks)
-    net.load_tensors(W.init_weights(arch, n=n, blocks=blocks, seed=123))
+    if rnd:
+        from test_gpu_uncertainty import rnd_fixture
+
+        net.load_tensors(rnd_fixture(oracle, rnd)["w"])
+    else:
+        net.load_tensors(W.init_weights(arch, n=n, blocks=blocks, seed=123))
     gpu = A.BatchedMCTS(B, n, 4, agent=net, node_capacity=1 << 14)
     ora = O.OracleSearch(oracle, B, n, 4, agent_kind=0, agent_fn=_agent_over(net))
     rng = np.random.default_rng(2024)
