@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — self-play throughput of the MI355X engine on BASELINE.json's north-star configuration.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 Workload (configs[1]): 5x5 Tak, half-komi 4, 4096 concurrent games per GPU,
 400 simulations per move, classic PUCT + Dirichlet(alpha 0.05, ratio 0.2), beta 0, net5 (20 residual
@@ -22,6 +22,11 @@ up on some rank, all ranks agree (one all-reduce) to hand the targets over throu
 ring - and the line's `exchange` says so with every rank's error; TZ_BENCH_EXCHANGE=native makes that an exit code 4 too.
 
 Prints ONE JSON line (rank 0).  `value` = MCTS simulations/s summed over all ranks.
+
+A plain run sets up, warms up, times the steps and prints the line: the headline figures and the `roofline` of the timed
+steps' own net-kernel events.  --full (N = 1) adds what takes runs of its own after the timed steps: the Agent surface's
+per-call times (`agent_surface`), the CPU stand-in (`cpu_baseline`) and the other precisions' throughput and measured
+errors (`precisions`, `within_1e-3_at_trained_scale`); --no-cpu-baseline / --no-precision-report leave parts of it out.
 
 --dump-outputs DIR: after the timed steps rank 0 writes what the last timed step handed back (dump_outputs / step_outputs)
 as DIR/<name>.npy, so that two builds can be compared output for output on the same seeded inputs.
@@ -287,7 +292,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--games", type=int, default=GAMES)
     ap.add_argument("--sims", type=int, default=None, help="simulations per move (default %d; 768 with --search gumbel, whose budget must be a multiple of k*log2 k)" % SIMS)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the timed steps also measure the Agent surface, the CPU stand-in and the other precisions "
+                         "(each in runs of its own; a plain run prints the headline figures alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU stand-in")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--capacity", type=int, default=0)
     ap.add_argument("--search", choices=["puct", "gumbel"], default="puct",
@@ -303,7 +311,7 @@ def main():
                          "trained logit scale, ~2.3x the f16 kernel time); f16x2 = split precision (hi/lo fp16 operands, 3 MFMAs per "
                          "product: 2.4e-5, ~3x); bf16 = the f16 kernels 5 %% faster at 1e-3 .. 7e-3 (random-init scale)")
     ap.add_argument("--no-precision-report", action="store_true",
-                    help="skip the second measurement (N = 1 only): throughput of the other precision and the measured logit errors")
+                    help="with --full: skip the Agent surface and the other precisions' throughput and measured logit errors")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     args = ap.parse_args()
@@ -489,7 +497,8 @@ def main():
                                             "dominant_kernel": prof["conv_ms"] / max(1, prof["steps"]),
                                             "wall": 1000.0 * dt / max(1.0, (sims1 - sims0) / args.games)}
             out["net_flops_frac_of_peak"] = (evals / dt_max) * FLOP_PER_POSITION / (world * PEAK_BF16_TFLOPS * 1e12)
-        if world == 1 and not args.no_precision_report and args.games >= 256:
+        full = args.full and world == 1
+        if full and not args.no_precision_report and args.games >= 256:
             # the Agent surface on its own (tz_net_eval: host states and legal moves in, host logits / value / variance out), the drop-in point
             # for a host that keeps the reference's CPU BatchedMCTS: per call at the reference's batch of 128 (selfplay/src/main.rs:37) and at 1.
             # Not part of `value`.
@@ -521,12 +530,12 @@ def main():
                     out["agent_surface"]["batch_%d" % b] = {"ms_per_call": 1000.0 * per, "positions_per_s": b / per}
             except Exception as e:
                 out["agent_surface"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline()
             except Exception as e:  # the checker must not take the measurement down with it
                 out["cpu_baseline"] = {"error": repr(e)}
-        if world == 1 and not args.no_precision_report and args.games == GAMES and args.precision in ("f16", "f16c6", "f16c8", "f16x2"):
+        if full and not args.no_precision_report and args.games == GAMES and args.precision in ("f16", "f16c6", "f16c8", "f16x2"):
             # the other precision's throughput and both measured errors: close the first engine (66 GB of pools)
             sp.close()
             mcts.close()

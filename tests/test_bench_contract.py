@@ -59,6 +59,24 @@ def test_dumped_outputs_are_the_same_from_run_to_run(tmp_path):
     assert a["root_visit_count"].shape == (256,) and a["positions"].shape[0] == 256 and a["child_visits"].sum() > 0
 
 
+@pytest.mark.gpu
+def test_plain_run_leaves_out_what_full_adds():
+    """A plain run prints the headline figures alone; --full adds what takes runs of its own after the timed steps (here
+    the Agent surface: the CPU stand-in is switched off, and the other precisions run at the full 4096 games only)."""
+    outs = []
+    for flags in ([], ["--full", "--no-cpu-baseline"]):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--games", "256",
+               "--sims", "16"] + flags
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        outs.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0]))
+    plain, full = outs
+    assert not {"agent_surface", "cpu_baseline", "precisions", "within_1e-3_at_trained_scale"} & set(plain)
+    assert isinstance(plain["roofline"], dict) and plain["value"] > 0
+    assert "cpu_baseline" not in full and "error" not in full["agent_surface"]
+    assert full["agent_surface"]["batch_128"]["ms_per_call"] > 0 and full["agent_surface"]["batch_1"]["ms_per_call"] > 0
+
+
 def test_dump_outputs_keeps_a_fixed_sample_under_the_limit(tmp_path):
     import numpy as np
 

@@ -33,5 +33,5 @@ unset TZ_PRECISION
 python3 tools/run_configs.py 4 > $O/r03_config4_f16_line.json 2>> $O/r03_config4.err || exit 1
 cat $O/r03_config4_f16c6_line.json $O/r03_net6_f16c6_bench.json $O/r03_net6_f16c6_pmc.csv $O/r03_config4_f16_line.json
 # the driver's own line
-python3 bench.py > $O/r03_bench_line.json 2> $O/r03_bench.err || exit 1
+python3 bench.py --full > $O/r03_bench_line.json 2> $O/r03_bench.err || exit 1
 cut -c1-1500 $O/r03_bench_line.json
