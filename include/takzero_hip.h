@@ -403,6 +403,11 @@ int tz_trainer_shape(tz_trainer* t, int* board_n_out, int* batch_out, int* arch_
  * writes it or the .tzw container; variables the step never touches (RND nets, SimHash matrix) are carried through. */
 int tz_trainer_load(tz_trainer* t, const char* path);
 int tz_trainer_save(tz_trainer* t, const char* path);
+/* tz_trainer_load from a .tzw container in memory (as tz_net_load_weights_mem) */
+int tz_trainer_load_weights_mem(tz_trainer* t, const void* data, size_t bytes);
+/* the carried variables (those the step never touches) as a .tzw container; bytes_out = its size, written to out only when
+ * out is not NULL and cap holds it */
+int tz_trainer_get_extras(tz_trainer* t, void* out, uint64_t cap, uint64_t* bytes_out);
 /* the variables of a network (tz_net_init_random = Net::new, or a loaded model) become the trainer's, and back */
 int tz_trainer_from_net(tz_trainer* t, tz_net* net);
 int tz_trainer_to_net(tz_trainer* t, tz_net* net);

@@ -39,7 +39,7 @@ SYMBOLS = [
     "tz_net_init_random", "tz_net_load_partial", "tz_net_save", "tz_net_clone", "tz_net_get_tensor", "tz_weights_convert", "tz_net_tensor_count", "tz_net_tensor_info",
     "tz_comm_unique_id", "tz_comm_rendezvous_id", "tz_comm_create_rccl", "tz_comm_create_fs", "tz_comm_destroy", "tz_comm_info",
     "tz_comm_all_gather", "tz_comm_take", "tz_comm_broadcast", "tz_comm_barrier", "tz_net_broadcast", "tz_selfplay_set_comm", "tz_selfplay_exchange",
-    "tz_trainer_load", "tz_trainer_save", "tz_trainer_from_net", "tz_trainer_to_net", "tz_learn_set_save_points",
+    "tz_trainer_load", "tz_trainer_save", "tz_trainer_load_weights_mem", "tz_trainer_get_extras", "tz_trainer_from_net", "tz_trainer_to_net", "tz_learn_set_save_points",
     "tz_learn_create", "tz_learn_destroy", "tz_learn_feed", "tz_learn_add_lines", "tz_learn_buffer_len", "tz_learn_step", "tz_learn_run", "tz_learn_last_batch",
 ]
 
@@ -98,6 +98,8 @@ def load():
     lib.tz_selfplay_exchange.argtypes = [vp]
     lib.tz_trainer_load.argtypes = [vp, C.c_char_p]
     lib.tz_trainer_save.argtypes = [vp, C.c_char_p]
+    lib.tz_trainer_load_weights_mem.argtypes = [vp, vp, C.c_size_t]
+    lib.tz_trainer_get_extras.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.tz_trainer_from_net.argtypes = [vp, vp]
     lib.tz_trainer_to_net.argtypes = [vp, vp]
     lib.tz_learn_set_save_points.argtypes = [vp, ci, ci, vp]

@@ -1297,6 +1297,25 @@ int tz_trainer_load(tz_trainer* t, const char* path) {
     return trainer_apply_store(t, st);
 }
 
+// the same from a .tzw container in memory (how the Python wrapper hands over a dict of tensors, extras included)
+int tz_trainer_load_weights_mem(tz_trainer* t, const void* data, size_t bytes) {
+    if (!t || !data) return tz_fail(TZ_EINVAL, "tz_trainer_load_weights_mem: null argument");
+    TensorStore st;
+    int rc = tzw_parse(static_cast<const unsigned char*>(data), bytes, st);
+    if (rc) return rc;
+    return trainer_apply_store(t, st);
+}
+
+// the carried variables alone as a .tzw container: out = NULL (or cap too small) asks for the size only
+int tz_trainer_get_extras(tz_trainer* t, void* out, uint64_t cap, uint64_t* bytes_out) {
+    if (!t) return tz_fail(TZ_EINVAL, "tz_trainer_get_extras: null handle");
+    std::vector<unsigned char> blob;
+    tzw_dump(t->extra, blob);
+    if (bytes_out) *bytes_out = blob.size();
+    if (out && cap >= blob.size()) memcpy(out, blob.data(), blob.size());
+    return TZ_OK;
+}
+
 int tz_trainer_save(tz_trainer* t, const char* path) {
     if (!t || !path) return tz_fail(TZ_EINVAL, "tz_trainer_save: null argument");
     TensorStore st;

@@ -55,8 +55,20 @@ class Trainer:
         for i in range(self.lib.tz_trainer_tensor_count(self.h)):
             check(self.lib.tz_trainer_tensor_info(self.h, i, buf, 256, C.byref(cnt)))
             self.names[buf.value.decode()] = int(cnt.value)
-        self.extra = {}     # tensors the step never touches (RND nets, SimHash matrix): carried through unchanged
-        self.shapes = {}
+        self.shapes = {name: self._shape(name, count) for name, count in self.names.items()}
+
+    def _shape(self, name, count):
+        """The variable's shape in the reference's VarStore (param_dims in csrc/tz_learn.hip), whichever way it was loaded."""
+        from . import weights as W
+
+        if name in ("value.conv2d.weight", "ube.conv2d.weight"):
+            return (1, count, 1, 1)
+        if name.endswith("conv2d.weight"):
+            co = W.output_channels(self.n) if name.startswith("policy.") else W.FILTERS
+            return (co, count // (9 * co), 3, 3)
+        if name.endswith(".linear.weight"):
+            return (1, count)
+        return (count,)
 
     def close(self):
         if self.h:
@@ -70,17 +82,16 @@ class Trainer:
             pass
 
     def load_tensors(self, tensors):
-        """VarStore contents by name (takzero_amd.weights / takzero_amd.ot)."""
+        """VarStore contents by name (takzero_amd.weights / takzero_amd.ot).  The tensors the step never touches (RND nets,
+        SimHash matrix) go to the library with the rest, so save / to_net / the native save points carry them."""
+        from .weights import dumps_tzw
+
         missing = [k for k in self.names if k not in tensors]
         if missing:
             raise ValueError("missing tensors: %s" % missing[:4])
-        for name, arr in tensors.items():
-            a = np.ascontiguousarray(arr, np.float32)
-            if name in self.names:
-                self.shapes[name] = a.shape
-                check(self.lib.tz_trainer_set_tensor(self.h, name.encode(), PARAM, a.ctypes.data, a.size))
-            else:
-                self.extra[name] = a.copy()
+        blob = dumps_tzw(tensors)
+        buf = (C.c_char * len(blob)).from_buffer_copy(blob)
+        check(self.lib.tz_trainer_load_weights_mem(self.h, C.addressof(buf), len(blob)))
         return self
 
     def load(self, path):
@@ -104,10 +115,20 @@ class Trainer:
         check(self.lib.tz_trainer_get_tensor(self.h, name.encode(), what, out.ctypes.data, out.size))
         return out.reshape(self.shapes.get(name, out.shape))
 
+    def extras(self):
+        """The variables the step never touches (RND nets, SimHash matrix), as the library carries them."""
+        from .weights import loads_tzw
+
+        size = C.c_uint64()
+        check(self.lib.tz_trainer_get_extras(self.h, None, 0, C.byref(size)))
+        buf = (C.c_char * size.value)()
+        check(self.lib.tz_trainer_get_extras(self.h, C.addressof(buf), size.value, C.byref(size)))
+        return loads_tzw(bytes(buf))
+
     def tensors(self):
         """Current weights by name, ready for Net.load_tensors / weights.save_tzw."""
         out = {name: self.tensor(name) for name in self.names}
-        out.update(self.extra)
+        out.update(self.extras())
         return out
 
     def step(self, states, policy, mask, value, ube, train_ube=True, apply=True):

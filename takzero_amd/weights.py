@@ -64,7 +64,11 @@ def dumps_tzw(tensors):
 
 
 def load_tzw(path):
-    data = open(path, "rb").read()
+    with open(path, "rb") as f:
+        return loads_tzw(f.read())
+
+
+def loads_tzw(data):
     assert data[:4] == b"TZW1"
     (count,) = struct.unpack_from("<I", data, 4)
     off, out = 8, {}

@@ -114,8 +114,16 @@ def test_trained_weights_feed_the_inference_net():
     trained = tr.tensors()
     assert set(trained) == set(w)
     net = A.Net(arch=A.ARCH_TEST, n=n, precision=A.PREC_F32, blocks=blocks).load_tensors(trained)
-    pol, val, _ = net.forward_raw(states)
+    pol, val, ube_out = net.forward_raw(states)
     assert np.isfinite(pol).all() and np.isfinite(val).all()
+    # ... and that forward is an eval-mode forward of the same tensors: oracle/nets_torch.py in fp64, running statistics in place
+    import nets_torch as NT
+
+    tp, tv, tu = NT.forward({k: np.asarray(v, np.float64) for k, v in trained.items()}, planes.astype(np.float64), blocks)
+    err = max(float(np.abs(pol - tp.reshape(B, -1).numpy()).max()), float(np.abs(val - tv.numpy()).max()),
+              float(np.abs(ube_out - tu.numpy()).max()))
+    print("PREC_F32 forward of the trained tensors against fp64 eval mode: %.3g" % err)
+    assert err <= 1e-3, err   # the product's bar for the fp32 path (measured 4.5e-7)
 
 
 def test_trainer_rejects_bad_arguments():
