@@ -108,6 +108,28 @@ def simhash_indices(w, planes, cin, return_dots=False):
         return (idx, dots.numpy()) if return_dots else idx
 
 
+def simhash_dots(w, planes, dtype=torch.float64):
+    """The 32 projections of get_indices (net6_simhash.rs:202-233) in `dtype` throughout: the colour plane cin - 2 zeroed,
+    view(-1, cin * n * n) @ simhash_matrix.  [B, 32]; bit j of a position's index is set where column j is not below zero."""
+    x = torch.from_numpy(np.array(planes, dtype=np.float32, copy=True))
+    with torch.no_grad():
+        x[:, x.shape[1] - 2] = 0.0
+        return x.reshape(x.shape[0], -1).to(dtype) @ _t(w, "simhash_matrix").to(dtype)
+
+
+def simhash_margin(w, planes):
+    """Per (position, bit) the a-priori bound on the error of an fp32 evaluation of that projection, whatever the order of the
+    sum and with or without FMA: K * 2**-24 * (|x| @ |matrix|), K = cin * n * n terms, 2**-24 the unit roundoff (every one of
+    the K - 1 additions and K products is off by at most one relative unit roundoff of a partial result no larger than
+    sum |x_k m_k|; K u bounds the compounded (1 + u)**K - 1 to first order, and the planes are mostly zero, which adds nothing).
+    Derived, not measured.  fp64, [B, 32].  A bit is decided where |simhash_dots| exceeds it."""
+    x = torch.from_numpy(np.array(planes, dtype=np.float32, copy=True))
+    with torch.no_grad():
+        x[:, x.shape[1] - 2] = 0.0
+        flat = x.reshape(x.shape[0], -1).to(torch.float64)
+        return flat.shape[1] * 2.0 ** -24 * (flat.abs() @ _t(w, "simhash_matrix").to(torch.float64).abs())
+
+
 def variance(w, planes, ube, arch, seen=None):
     """net5.rs:271-278 / net6_simhash.rs:311-318."""
     with torch.no_grad():
