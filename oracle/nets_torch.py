@@ -20,31 +20,33 @@ def _t(w, name):
     return torch.from_numpy(np.ascontiguousarray(w[name]))
 
 
-def _bn(x, w, p):
-    return F.batch_norm(x, _t(w, p + ".running_mean"), _t(w, p + ".running_var"), _t(w, p + ".weight"),
-                        _t(w, p + ".bias"), training=False, eps=1e-5)
-
-
-def _small_block(x, w, p):  # residual.rs:13-37
-    return _bn(F.conv2d(x, _t(w, p + ".conv2d.weight"), padding=1), w, p + ".batch_norm")
-
-
-def forward(w, planes, blocks):
-    """planes [B,C,N,N] fp32 -> (policy [B,OUT,N,N], value [B], ube [B]); net5.rs:184-191."""
+def forward(w, planes, blocks, dtype=torch.float32, trace=None):
+    """planes [B,C,N,N] fp32 -> (policy [B,OUT,N,N], value [B], ube [B]); net5.rs:184-191.  `dtype` is the arithmetic of the
+    whole graph (fp32 as the reference runs it, or torch.float64: every tensor converted, eps added in double).  `trace`, a
+    list, receives (name, tensor) for every stored trunk activation - "core.input", "core.res_block_i.a" (after its ReLU),
+    "core.res_block_i" (the block's output) - and for the heads' outputs before tanh ("value.pre", "ube.pre")."""
     x = torch.from_numpy(planes) if isinstance(planes, np.ndarray) else planes
+    p_ = lambda name: _t(w, name).to(dtype)
+    bn = lambda x, p: F.batch_norm(x, p_(p + ".running_mean"), p_(p + ".running_var"), p_(p + ".weight"), p_(p + ".bias"),
+                                   training=False, eps=1e-5)
+    keep = (lambda name, t: trace.append((name, t))) if trace is not None else (lambda name, t: None)
     with torch.no_grad():
-        x = F.relu(_bn(F.conv2d(x, _t(w, "core.input_conv2d.weight"), padding=1), w, "core.batch_norm"))
+        x = F.relu(bn(F.conv2d(x.to(dtype), p_("core.input_conv2d.weight"), padding=1), "core.batch_norm"))
+        keep("core.input", x)
         for b in range(blocks):
             p = "core.res_block_%d" % b
-            y = _small_block(x, w, p + ".a")
-            y = _small_block(F.relu(y), w, p + ".b")
+            y = F.relu(bn(F.conv2d(x, p_(p + ".a.conv2d.weight"), padding=1), p + ".a.batch_norm"))   # residual.rs:13-37
+            keep(p + ".a", y)
+            y = bn(F.conv2d(y, p_(p + ".b.conv2d.weight"), padding=1), p + ".b.batch_norm")
             x = F.relu(y + x)  # residual.rs:58-62
-        policy = F.conv2d(x, _t(w, "policy.conv2d.weight"), _t(w, "policy.conv2d.bias"), padding=1)
+            keep(p, x)
+        policy = F.conv2d(x, p_("policy.conv2d.weight"), p_("policy.conv2d.bias"), padding=1)
         heads = []
         for head in ("value", "ube"):
-            h = F.relu(F.conv2d(x, _t(w, head + ".conv2d.weight"), _t(w, head + ".conv2d.bias")))
+            h = F.relu(F.conv2d(x, p_(head + ".conv2d.weight"), p_(head + ".conv2d.bias")))
             h = h.view(h.shape[0], -1)
-            heads.append(F.linear(h, _t(w, head + ".linear.weight"), _t(w, head + ".linear.bias")).view(-1))
+            heads.append(F.linear(h, p_(head + ".linear.weight"), p_(head + ".linear.bias")).view(-1))
+            keep(head + ".pre", heads[-1])
         return policy, torch.tanh(heads[0]), heads[1]
 
 

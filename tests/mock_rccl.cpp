@@ -93,6 +93,27 @@ ncclResult_t ncclCommInitRank(ncclComm_t* comm, int nranks, ncclUniqueId id, int
     m->rank = rank;
     m->n = nranks;
     (void)mkdir(m->dir.c_str(), 0700);
+    // as ncclCommInitRank does, return only once every rank has joined: rank 0 removes the published id right after this call
+    // (tz_comm_create_rccl), and a rank that started later must have read it by then
+    const std::string mine = m->dir + "/join-" + std::to_string(rank);
+    FILE* f = fopen(mine.c_str(), "wb");
+    if (!f) {
+        delete m;
+        return ncclSystemError;
+    }
+    fclose(f);
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int r = 0; r < nranks; r++) {
+        const std::string other = m->dir + "/join-" + std::to_string(r);
+        struct stat st;
+        while (stat(other.c_str(), &st) != 0) {
+            if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 120.0) {
+                delete m;
+                return ncclSystemError;
+            }
+            std::this_thread::sleep_for(std::chrono::milliseconds(1));
+        }
+    }
     *comm = reinterpret_cast<ncclComm_t>(m);
     return ncclSuccess;
 }

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from exact_net import distinct_positions
 from gpu_util import random_positions, require_gpu
 
 pytestmark = pytest.mark.gpu
@@ -282,8 +283,7 @@ def test_workgroup_forms_of_the_split_precisions_on_6x6_give_the_same_bits(oracl
 
     net = A.Net(arch=A.ARCH_NET6_SIMHASH, precision=prec)
     net.load_tensors(W.init_weights(W.ARCH_NET6_SIMHASH, seed=9))
-    base = O.states_array(random_positions(oracle, O, 6, 4, 64, 23))
-    states = np.concatenate([base] * 18)[:1100]
+    states = O.states_array(distinct_positions(oracle, O, 6, 1100, 23))     # all different: a board taken from another group's place shows
     big = net.forward_raw(states)
     for count in (1027, 300, 5):
         part = net.forward_raw(states[:count])
@@ -302,8 +302,7 @@ def test_workgroup_forms_give_the_same_bits(oracle, prec):
 
     net = A.Net(arch=A.ARCH_NET5, precision=prec)
     net.load_tensors(W.init_weights(W.ARCH_NET5, seed=9))
-    base = O.states_array(random_positions(oracle, O, 5, 4, 64, 21))
-    states = np.concatenate([base] * 18)[:1100]
+    states = O.states_array(distinct_positions(oracle, O, 5, 1100, 21))     # all different: a board taken from another group's place shows
     big = net.forward_raw(states)                      # > 1024 positions: the full-size workgroups
     for count in (1030, 600, 300, 100):                # full size again (ragged), 4, 2 and 1 boards per workgroup
         part = net.forward_raw(states[:count])
