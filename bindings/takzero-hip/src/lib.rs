@@ -182,6 +182,19 @@ impl<const B: usize> HipBatchedMCTS<B> {
     pub fn simulate(&mut self, betas: &[f32]) {
         check(unsafe { sys::tz_search_simulate(self.raw, betas.as_ptr(), 1) }).unwrap();
     }
+    /// Node::simulate_batch (mcts.rs:268-328) on every root, `rounds` times: up to `leaves` leaves per tree and round, one
+    /// network call for the leaves of all trees (tei/src/main.rs:253, analysis/src/main.rs:35,78 with one tree and 128 leaves)
+    pub fn simulate_batch(&mut self, betas: &[f32], leaves: usize, rounds: usize) {
+        check(unsafe { sys::tz_search_simulate_batch(self.raw, betas.as_ptr(), leaves as i32, rounds as i32) }).unwrap();
+    }
+    /// Node::principal_variation (node/mod.rs:40-62, 87-90) of one root, as move indices
+    pub fn principal_variation(&self, game: usize) -> Vec<u16> {
+        let mut out = vec![0u16; 512];
+        let mut len = 0i32;
+        check(unsafe { sys::tz_search_principal_variation(self.raw, game as i32, out.as_mut_ptr(), out.len() as i32, &mut len) }).unwrap();
+        out.truncate((len as usize).min(512));
+        out
+    }
     pub fn root_info(&self) -> Vec<sys::TzRootInfo> {
         let zero = sys::TzRootInfo { visit_count: 0, n_children: 0, eval_tag: 0, is_terminal_env: 0, ply: 0, eval_bits: 0, std_dev: 0.0, logit: 0.0, probability: 0.0 };
         let mut out = vec![zero; B];

@@ -213,6 +213,27 @@ int tz_search_new_openings(tz_search* s, const int32_t* opening_choice);
 /* BatchedMCTS::simulate called n_sims times (batched.rs:63-128); betas[batch]. Asynchronous
  * on the handle's stream; any later call that returns data synchronises. */
 int tz_search_simulate(tz_search* s, const float* betas, int n_sims);
+/* Node::simulate_batch (mcts.rs:268-328) applied to every root of the handle, `rounds` times: the search of the reference's tei and
+ * analysis binaries (tei/src/main.rs:253, analysis/src/main.rs:35,78), which fills a network batch from one tree.  Per tree and
+ * round: up to 4*leaves forwards (mcts.rs:281); Known results are backed up at once (:284); the loop ends when `leaves` leaves
+ * need the network (:297).  One network call covers all trees' leaves.  backward_network_eval then runs per tree in collection
+ * order (:307-327); a leaf collected more than once in a round is evaluated each time and its children are replaced each time
+ * (mcts.rs:199-217), as in the reference.  betas[batch].  Asynchronous like tz_search_simulate.
+ * tz_search_counters: simulations grow by the forwards actually made, nn_leaf_evals by the leaves sent to the network.
+ * TZ_EINVAL: leaves < 1, rounds < 0, a null pointer, or batch * leaves > TZ_SIMULATE_BATCH_MAX_SLOTS.  Scratch for batch * leaves
+ * leaf slots is allocated at the first call and grown on demand.  A full node pool behaves as in tz_search_simulate
+ * (tz_search_pool_overflows).  The virtual_visits counter of the reference's `virtual` feature is not kept: selection does not
+ * read it (the code that would is commented out, node/mod.rs:115-122) and it is back at zero after every call. */
+#define TZ_SIMULATE_BATCH_MAX_SLOTS 16384
+int tz_search_simulate_batch(tz_search* s, const float* betas, int leaves, int rounds);
+/* Where the rounds of tz_search_simulate_batch spent their time since profiling was switched on (tz_search_profile with reset 1;
+ * reset 1 or 2 also clears these): HIP-event time in ms of the forward kernel with the compaction, of the network call, and of
+ * the backward pass with the leaf softmax, summed over `rounds` rounds.  Any pointer may be NULL. */
+int tz_search_batch_profile(tz_search* s, double* forward_ms, double* net_ms, double* backward_ms, uint64_t* rounds);
+/* Node::principal_variation (node/mod.rs:40-62, 87-90) of one root.  Follows select_best_action until a node needs
+ * initialisation or is terminal.  moves_out[cap] receives move indices.  len_out receives the full length, even when it
+ * exceeds cap. */
+int tz_search_principal_variation(tz_search* s, int game, uint16_t* moves_out, int cap, int* len_out);
 /* BatchedMCTS::apply_noise with caller-supplied Dirichlet samples (noise.rs:10-26):
  * noise[batch][amax], row g holds one sample of dimension n_children(g). */
 int tz_search_apply_noise(tz_search* s, const float* noise, int amax, float ratio);

@@ -41,6 +41,7 @@ SYMBOLS = [
     "tz_comm_all_gather", "tz_comm_take", "tz_comm_broadcast", "tz_comm_barrier", "tz_net_broadcast", "tz_selfplay_set_comm", "tz_selfplay_exchange",
     "tz_trainer_load", "tz_trainer_save", "tz_trainer_load_weights_mem", "tz_trainer_get_extras", "tz_trainer_from_net", "tz_trainer_to_net", "tz_learn_set_save_points",
     "tz_learn_create", "tz_learn_destroy", "tz_learn_feed", "tz_learn_add_lines", "tz_learn_buffer_len", "tz_learn_step", "tz_learn_run", "tz_learn_last_batch",
+    "tz_search_simulate_batch", "tz_search_principal_variation", "tz_search_batch_profile",
 ]
 
 _lib = None
@@ -116,6 +117,9 @@ def load():
     lib.tz_search_get_positions.argtypes = [vp, vp]
     lib.tz_search_new_openings.argtypes = [vp, vp]
     lib.tz_search_simulate.argtypes = [vp, vp, ci]
+    lib.tz_search_simulate_batch.argtypes = [vp, vp, ci, ci]
+    lib.tz_search_batch_profile.argtypes = [vp] + [C.POINTER(C.c_double)] * 3 + [C.POINTER(C.c_uint64)]
+    lib.tz_search_principal_variation.argtypes = [vp, ci, vp, ci, C.POINTER(ci)]
     lib.tz_search_apply_noise.argtypes = [vp, vp, ci, cf]
     lib.tz_search_root_info.argtypes = [vp, vp]
     lib.tz_search_root_children.argtypes = [vp, ci] + [vp] * 7

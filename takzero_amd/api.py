@@ -277,6 +277,13 @@ class BatchedMCTS:
         assert b.shape == (self.batch,)
         check(self.lib.tz_search_simulate(self.h, b.ctypes.data, n_sims))
 
+    def simulate_batch(self, betas, leaves, rounds=1):
+        """Node::simulate_batch (mcts.rs:268-328) on every root, `rounds` times: each tree collects up to `leaves` leaves per
+        round (tei / analysis use 128 on one tree) and one network call evaluates the leaves of all trees."""
+        b = np.ascontiguousarray(betas, dtype=np.float32)
+        assert b.shape == (self.batch,)
+        check(self.lib.tz_search_simulate_batch(self.h, b.ctypes.data, leaves, rounds))
+
     def apply_noise(self, noise, ratio):
         nz = np.ascontiguousarray(noise, dtype=np.float32)
         assert nz.ndim == 2 and nz.shape[0] == self.batch
@@ -327,6 +334,19 @@ class BatchedMCTS:
         out = np.zeros(self.batch, np.uint16)
         check(self.lib.tz_search_select_best_actions(self.h, out.ctypes.data))
         return out
+
+    def batch_profile(self):
+        """HIP-event split of the simulate_batch rounds run since profile(1): forward, network, backward (ms) and the round count"""
+        f, n, b, r = C.c_double(), C.c_double(), C.c_double(), C.c_uint64()
+        check(self.lib.tz_search_batch_profile(self.h, C.byref(f), C.byref(n), C.byref(b), C.byref(r)))
+        return dict(forward_ms=f.value, net_ms=n.value, backward_ms=b.value, rounds=r.value)
+
+    def principal_variation(self, game):
+        """Node::principal_variation (node/mod.rs:40-62, 87-90) of one root: move indices, best first."""
+        out = np.zeros(512, np.uint16)
+        n = C.c_int(0)
+        check(self.lib.tz_search_principal_variation(self.h, game, out.ctypes.data, len(out), C.byref(n)))
+        return out[:min(n.value, len(out))].copy()
 
     def select_actions_in_selfplay(self, rng, weighted_random_steps, threshold=32, allowed_eval_drop=0.5):
         """batched.rs:165-183 / node/mod.rs:170-207 with a numpy Generator in place of the Rust rng

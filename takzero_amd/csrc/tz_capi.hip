@@ -1,6 +1,7 @@
 // tz_capi.hip — BatchedMCTS surface of the C ABI (include/takzero_hip.h) over the tree kernels
 // (tz_tree.hip) and the network (tz_nn.hip).  Reference: takzero/src/search/node/batched.rs:32-409.
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -31,6 +32,13 @@ struct tz_search {
     uint64_t graph_gen[2] = {0, 0};  // tz_net::weights_gen the graph was captured with
     bool use_graph = true;
     uint64_t sim_index = 0;
+    // tz_search_simulate_batch: leaf slots, allocated at first use and grown on demand
+    LeafBatchDev lb = {};
+    size_t lb_slots = 0;
+    // with profiling on, HIP events around the three parts of every round: forward (+ compaction), network, backward
+    std::vector<std::array<hipEvent_t, 4>> batch_events;
+    double batch_ms[3] = {0.0, 0.0, 0.0};
+    uint64_t batch_rounds = 0;
     // profiling
     bool profile = false;
     double tree_ms = 0.0;
@@ -170,6 +178,90 @@ int ensure_noise(tz_search* s, int amax) {
     return TZ_OK;
 }
 
+void free_leaf_batch(tz_search* s) {
+    LeafBatchDev& b = s->lb;
+    void* ptrs[] = {b.env, b.act, b.nact, b.traj, b.traj_len, b.logit, b.prob, b.value, b.variance, b.bad, b.count, b.forwards,
+                    b.offset, b.index};
+    for (void* p : ptrs)
+        if (p) (void)hipFree(p);
+    b = LeafBatchDev{};
+    s->lb_slots = 0;
+}
+
+// scratch for batch * leaves leaf slots, and the network's work buffers for as many positions
+int ensure_leaf_batch(tz_search* s, int leaves) {
+    const size_t slots = (size_t)s->d.batch * leaves;
+    if (slots > s->lb_slots) {
+        TZ_HIP(hipStreamSynchronize(s->stream));
+        free_leaf_batch(s);
+        LeafBatchDev& b = s->lb;
+        const size_t amax = (size_t)s->d.max_actions;
+        int rc = 0;
+        rc |= dev_alloc(&b.env, slots);
+        rc |= dev_alloc(&b.act, slots * amax);
+        rc |= dev_alloc(&b.nact, slots);
+        rc |= dev_alloc(&b.traj, slots * TZ_MAX_DEPTH);
+        rc |= dev_alloc(&b.traj_len, slots);
+        rc |= dev_alloc(&b.logit, slots * amax);
+        rc |= dev_alloc(&b.prob, slots * amax);
+        rc |= dev_alloc(&b.value, slots);
+        rc |= dev_alloc(&b.variance, slots);
+        rc |= dev_alloc(&b.bad, slots);
+        rc |= dev_alloc(&b.count, s->d.batch);
+        rc |= dev_alloc(&b.forwards, s->d.batch);
+        rc |= dev_alloc(&b.offset, s->d.batch);
+        rc |= dev_alloc(&b.index, slots);
+        if (rc) {
+            free_leaf_batch(s);
+            return tz_fail(TZ_ENOMEM, "tz_search_simulate_batch: device allocation failed (lower leaves)");
+        }
+        s->lb_slots = slots;
+    }
+    s->lb.leaves = leaves;
+    if (s->net && (int)slots > s->net->max_batch) {
+        int rc = tz_net_ensure_batch(s->net, (int)slots);
+        if (rc) return rc;
+        s->net->weights_gen++;  // the captured lock-step graphs of every handle on this net point at the buffers just replaced
+    }
+    return TZ_OK;
+}
+
+int drain_batch_profile(tz_search* s) {
+    for (auto& ev : s->batch_events) {
+        for (int i = 0; i < 3; i++) {
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) s->batch_ms[i] += ms;
+        }
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+        s->batch_rounds++;
+    }
+    s->batch_events.clear();
+    return TZ_OK;
+}
+
+// one round of Node::simulate_batch (mcts.rs:268-328) on every root
+int one_batch_round(tz_search* s) {
+    int rc;
+    std::array<hipEvent_t, 4> ev = {nullptr, nullptr, nullptr, nullptr};
+    if (s->profile) {
+        for (hipEvent_t& e : ev) TZ_HIP(hipEventCreate(&e));
+        s->batch_events.push_back(ev);
+        TZ_HIP(hipEventRecord(ev[0], s->stream));
+    }
+    if ((rc = tz_tree_descend_batch(s->d, s->lb, s->stream))) return rc;
+    if ((rc = tz_tree_compact_batch(s->d, s->lb, s->stream))) return rc;
+    if (s->profile) TZ_HIP(hipEventRecord(ev[1], s->stream));
+    NetOut out{nullptr, 0, nullptr, nullptr};
+    if (s->d.agent_kind == TZ_AGENT_NET) {
+        if ((rc = tz_net_forward_device(s->net, s->lb.env, s->lb.index, s->d.nn_count, 0, s->d.batch * s->lb.leaves, s->stream, &out)))
+            return rc;
+    }
+    if (s->profile) TZ_HIP(hipEventRecord(ev[2], s->stream));
+    if ((rc = tz_tree_expand_batch(s->d, s->lb, out, s->stream))) return rc;
+    if (s->profile) TZ_HIP(hipEventRecord(ev[3], s->stream));
+    return TZ_OK;
+}
+
 int ensure_child(tz_search* s, size_t bytes) {
     if (bytes <= s->child_cap) return TZ_OK;
     if (s->child_dev) (void)hipFree(s->child_dev);
@@ -287,6 +379,8 @@ int tz_search_destroy(tz_search* s) {
                     s->noise_dev, s->act_dev, s->i32_dev, s->i8_dev, s->info_dev, s->child_dev};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    free_leaf_batch(s);
+    drain_batch_profile(s);
     if (s->own_stream && s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
     return TZ_OK;
@@ -342,6 +436,52 @@ int tz_search_simulate(tz_search* s, const float* betas, int n_sims) {
     int rc = check_error_flag(s);
     drain_profile(s);
     return rc;
+}
+
+int tz_search_simulate_batch(tz_search* s, const float* betas, int leaves, int rounds) {
+    if (!s || !betas || leaves < 1 || rounds < 0) return tz_fail(TZ_EINVAL, "tz_search_simulate_batch: bad argument");
+    if ((long long)s->d.batch * leaves > TZ_SIMULATE_BATCH_MAX_SLOTS)
+        return tz_fail(TZ_EINVAL, "tz_search_simulate_batch: batch * leaves exceeds TZ_SIMULATE_BATCH_MAX_SLOTS");
+    TZ_HIP(hipSetDevice(s->device));
+    int rc = ensure_leaf_batch(s, leaves);
+    if (rc) return rc;
+    TZ_HIP(hipMemcpyAsync(s->d.betas, betas, s->d.batch * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    for (int i = 0; i < rounds; i++)
+        if ((rc = one_batch_round(s))) return rc;
+    rc = check_error_flag(s);
+    drain_batch_profile(s);
+    return rc;
+}
+
+int tz_search_batch_profile(tz_search* s, double* forward_ms, double* net_ms, double* backward_ms, uint64_t* rounds) {
+    if (!s) return tz_fail(TZ_EINVAL, "tz_search_batch_profile: null argument");
+    TZ_HIP(hipSetDevice(s->device));
+    TZ_HIP(hipStreamSynchronize(s->stream));
+    drain_batch_profile(s);
+    if (forward_ms) *forward_ms = s->batch_ms[0];
+    if (net_ms) *net_ms = s->batch_ms[1];
+    if (backward_ms) *backward_ms = s->batch_ms[2];
+    if (rounds) *rounds = s->batch_rounds;
+    return TZ_OK;
+}
+
+int tz_search_principal_variation(tz_search* s, int game, uint16_t* moves_out, int cap, int* len_out) {
+    if (!s || game < 0 || game >= s->d.batch || cap < 0 || (cap && !moves_out) || !len_out)
+        return tz_fail(TZ_EINVAL, "tz_search_principal_variation: bad argument");
+    TZ_HIP(hipSetDevice(s->device));
+    const int n = std::min(cap, TZ_MAX_DEPTH);  // the walk ends at TZ_MAX_DEPTH moves
+    int rc = ensure_child(s, 64 + 2 * (size_t)TZ_MAX_DEPTH);
+    if (rc) return rc;
+    int* d_len = (int*)s->child_dev;
+    uint16_t* d_moves = (uint16_t*)((unsigned char*)s->child_dev + 64);
+    if ((rc = tz_tree_principal_variation(s->d, game, d_moves, n, d_len, s->stream))) return rc;
+    int len = 0;
+    TZ_HIP(hipMemcpyAsync(&len, d_len, sizeof len, hipMemcpyDeviceToHost, s->stream));
+    TZ_HIP(hipStreamSynchronize(s->stream));
+    const int have = std::min(len, n);
+    if (have) TZ_HIP(hipMemcpy(moves_out, d_moves, (size_t)have * 2, hipMemcpyDeviceToHost));
+    *len_out = len;
+    return TZ_OK;
 }
 
 int tz_search_apply_noise(tz_search* s, const float* noise, int amax, float ratio) {
@@ -747,6 +887,9 @@ int tz_search_profile(tz_search* s, int reset, double* conv_ms, uint64_t* conv_l
     if (tree_ms) *tree_ms = s->tree_ms;
     if (steps) *steps = s->steps;
     if (reset == 1 || reset == 2) {  // 1: reset and enable, 2: reset and disable
+        drain_batch_profile(s);
+        s->batch_ms[0] = s->batch_ms[1] = s->batch_ms[2] = 0.0;
+        s->batch_rounds = 0;
         s->tree_ms = 0.0;
         s->steps = 0;
         s->profile = reset == 1;

@@ -62,6 +62,26 @@ struct SearchDev {
     uint8_t* term_winner; // [batch] 0 white, 1 black, 2 draw
 };
 
+// Scratch of tz_search_simulate_batch (Node::simulate_batch, mcts.rs:268-328): `leaves` leaf slots per tree, slot (g, j) at index
+// g * leaves + j.  Tree g fills its slots j = 0, 1, ... in collection order; the backward pass takes them in that order.
+struct LeafBatchDev {
+    int leaves;
+    tz_state* env;       // [batch * leaves] leaf positions
+    uint16_t* act;       // [batch * leaves][max_actions] legal moves
+    uint16_t* nact;      // [batch * leaves]
+    uint32_t* traj;      // [batch * leaves][TZ_MAX_DEPTH] node indices, root first
+    uint32_t* traj_len;  // [batch * leaves]
+    float* logit;        // [batch * leaves][max_actions] agent logits of the legal moves
+    float* prob;         // [batch * leaves][max_actions] their softmax
+    float* value;        // [batch * leaves]
+    float* variance;     // [batch * leaves]
+    uint8_t* bad;        // [batch * leaves] the agent's outputs hold a NaN
+    int32_t* count;      // [batch] leaves collected in this round
+    int32_t* forwards;   // [batch] forwards made in this round
+    int32_t* offset;     // [batch] the tree's first slot in the net's outputs
+    int32_t* index;      // [batch * leaves] net slot -> leaf slot
+};
+
 // network outputs consumed by the expand kernel (device pointers, indexed by nn slot)
 struct NetOut {
     const float* policy;  // [slots][NN][policy_stride]  (NHWC: pixel-major, channel contiguous)
@@ -88,4 +108,8 @@ int tz_tree_restart(const SearchDev& s, const int32_t* choice_dev, int8_t* termi
 int tz_tree_reset_games(const SearchDev& s, const int32_t* idx_dev, int count, hipStream_t st);
 int tz_tree_set_start_children(const SearchDev& s, const int32_t* child_index_dev, hipStream_t st);
 int tz_tree_gumbel_root_fixup(const SearchDev& s, hipStream_t st);
+int tz_tree_principal_variation(const SearchDev& s, int game, uint16_t* moves_dev, int cap, int* len_dev, hipStream_t st);
+int tz_tree_descend_batch(const SearchDev& s, const LeafBatchDev& b, hipStream_t st);
+int tz_tree_compact_batch(const SearchDev& s, const LeafBatchDev& b, hipStream_t st);
+int tz_tree_expand_batch(const SearchDev& s, const LeafBatchDev& b, const NetOut& out, hipStream_t st);
 int tz_tree_play_moves(const SearchDev& s, const uint16_t* actions_dev, int8_t* ok_dev, hipStream_t st);

@@ -176,30 +176,13 @@ __device__ void backup(const SearchDev& s, size_t base, const uint32_t* tnode, c
 }
 
 // ---------------------------------------------------------------------------------------------
+// Node::forward, mcts.rs:107-138, from `node` with env at that node's position: the walk shared by descend_kernel (one forward per
+// launch) and descend_batch_kernel (a round of forwards per launch).  Records the path in tnode/tvis (LDS), leaves env at the leaf's
+// position.  Returns 0 Known (in `known`), 1 NeedsNetwork, 2 error (flag set); depth = nodes on the path.
 template <int N>
-__global__ __launch_bounds__(64) void descend_kernel(SearchDev s, int from_start) {
-    constexpr int NN = N * N;
-    const int g = blockIdx.x, l = lane_id();
-    __shared__ tz_state env;
-    __shared__ uint32_t tnode[TZ_MAX_DEPTH];
-    __shared__ uint32_t tvis[TZ_MAX_DEPTH];
-    __shared__ uint8_t reach[NN * 4];
-    load_state(&env, &s.env[g]);
-    const size_t base = slab_base(s, s.bank[g], g);
-    uint32_t node = 0;
-    float beta = s.betas[g];
-    if (from_start) {
-        node = (uint32_t)s.start_node[g];
-        beta = 0.0f;  // batched.rs:279
-    }
-    __syncthreads();
-    if (from_start && node != 0) {
-        apply_move<N>(&env, s.t.action[base + node]);
-        __syncthreads();
-    }
-    int depth = 0;
-    int kind = -1;  // 0 known, 1 needs network, 2 error
-    Ev known{0, 0};
+__device__ __forceinline__ int forward_walk(const SearchDev& s, size_t base, tz_state& env, uint32_t* tnode, uint32_t* tvis,
+                                            uint32_t node, float beta, int& depth, Ev& known) {
+    const int l = lane_id();
     for (;;) {
         const uint32_t vis = s.t.visits[base + node] + 1;
         if (l == 0) {
@@ -212,8 +195,7 @@ __global__ __launch_bounds__(64) void descend_kernel(SearchDev s, int from_start
         const int nc = s.t.nchild[base + node];
         if (ev_known(ev) && ev.bits == 0) {  // is_terminal, node/mod.rs:106-108
             known = ev;
-            kind = 0;
-            break;
+            return 0;
         }
         if (nc == 0 && !ev_known(ev)) {  // needs_initialization, node/mod.rs:83-85
             const int t = terminal<N>(&env);
@@ -224,16 +206,13 @@ __global__ __launch_bounds__(64) void descend_kernel(SearchDev s, int from_start
                     s.t.eval_bits[base + node] = 0;
                     s.t.std_dev[base + node] = 0.0f;
                 }
-                kind = 0;
-            } else {
-                kind = 1;
+                return 0;
             }
-            break;
+            return 1;
         }
         if (depth >= TZ_MAX_DEPTH) {
             if (l == 0) atomicMax(s.error_flag, 2);
-            kind = 2;
-            break;
+            return 2;
         }
         // select_with_puct, policy.rs:78-95 (ties -> last index: Iterator::max_by_key)
         const uint32_t c0 = s.t.child0[base + node];
@@ -266,13 +245,38 @@ __global__ __launch_bounds__(64) void descend_kernel(SearchDev s, int from_start
         }
         if (best_i < 0) {  // reference: expect("there should always be a child to simulate")
             if (l == 0) atomicMax(s.error_flag, 4);
-            kind = 2;
-            break;
+            return 2;
         }
         node = c0 + (uint32_t)best_i;
         apply_move<N>(&env, s.t.action[base + node]);
         __syncthreads();
     }
+}
+
+template <int N>
+__global__ __launch_bounds__(64) void descend_kernel(SearchDev s, int from_start) {
+    constexpr int NN = N * N;
+    const int g = blockIdx.x, l = lane_id();
+    __shared__ tz_state env;
+    __shared__ uint32_t tnode[TZ_MAX_DEPTH];
+    __shared__ uint32_t tvis[TZ_MAX_DEPTH];
+    __shared__ uint8_t reach[NN * 4];
+    load_state(&env, &s.env[g]);
+    const size_t base = slab_base(s, s.bank[g], g);
+    uint32_t node = 0;
+    float beta = s.betas[g];
+    if (from_start) {
+        node = (uint32_t)s.start_node[g];
+        beta = 0.0f;  // batched.rs:279
+    }
+    __syncthreads();
+    if (from_start && node != 0) {
+        apply_move<N>(&env, s.t.action[base + node]);
+        __syncthreads();
+    }
+    int depth = 0;
+    Ev known{0, 0};
+    const int kind = forward_walk<N>(s, base, env, tnode, tvis, node, beta, depth, known);  // 0 known, 1 needs network, 2 error
     __syncthreads();
     if (kind == 0) {
         // backward_known_eval, mcts.rs:141-163: the leaf itself is not updated
@@ -444,6 +448,251 @@ __global__ __launch_bounds__(64) void expand_kernel(SearchDev s, NetOut out) {
     backup(s, base, tnode, tvis, len - 1, ev_value(value * TZ_DISCOUNT), variance * TZ_DISCOUNT * TZ_DISCOUNT, ev_value(mean));
 }
 
+// ---------------------------------------------------------------------------------------------
+// Node::simulate_batch, mcts.rs:268-328, on every root of the handle: descend_batch_kernel (the forward loop of a round),
+// compact_batch_kernel, the network, leaf_policy_kernel (softmax per collected leaf), expand_batch_kernel (backward_network_eval per
+// tree in collection order).  Leaf slot (g, j) of LeafBatchDev is g * leaves + j.
+//
+// One wave per tree runs the forward loop of mcts.rs:281-300: up to 4 * leaves forwards, a Known result backed up at once (:284),
+// a leaf that needs the network written to the tree's next slot, until `leaves` are collected (:297).  A forward reads the visit
+// counts and solver results lane 0 stored in the forwards before it, hence the fence and barrier between trajectories.
+template <int N>
+__global__ __launch_bounds__(64) void descend_batch_kernel(SearchDev s, LeafBatchDev b) {
+    constexpr int NN = N * N;
+    const int g = blockIdx.x, l = lane_id();
+    __shared__ tz_state root_env;
+    __shared__ tz_state env;
+    __shared__ uint32_t tnode[TZ_MAX_DEPTH];
+    __shared__ uint32_t tvis[TZ_MAX_DEPTH];
+    __shared__ uint8_t reach[NN * 4];
+    load_state(&root_env, &s.env[g]);
+    const size_t base = slab_base(s, s.bank[g], g);
+    const float beta = s.betas[g];
+    int collected = 0, forwards = 0;
+    __syncthreads();
+    for (int f = 0; f < 4 * b.leaves && collected < b.leaves; f++) {
+        load_state(&env, &root_env);  // env.clone(), mcts.rs:283
+        __syncthreads();
+        int depth = 0;
+        Ev known{0, 0};
+        const int kind = forward_walk<N>(s, base, env, tnode, tvis, 0, beta, depth, known);
+        __syncthreads();
+        forwards++;
+        if (kind == 2) break;
+        if (kind == 0) {
+            backup(s, base, tnode, tvis, depth - 1, known, 0.0f, known);  // backward_known_eval, mcts.rs:141-163
+        } else {
+            const size_t slot = (size_t)g * b.leaves + collected;
+            uint16_t* acts = b.act + slot * s.max_actions;
+            const int nact = gen_moves<N>(&env, reach, acts, s.max_actions);  // env.populate_actions, mcts.rs:289
+            if (nact > s.max_actions && l == 0) atomicMax(s.error_flag, 3);
+            {
+                const uint32_t* a = reinterpret_cast<const uint32_t*>(&env);
+                uint32_t* d = reinterpret_cast<uint32_t*>(&b.env[slot]);
+                for (int i = l; i < (int)(sizeof(tz_state) / 4); i += 64) d[i] = a[i];
+            }
+            for (int i = l; i < depth; i += 64) b.traj[slot * TZ_MAX_DEPTH + i] = tnode[i];
+            if (l == 0) {
+                b.nact[slot] = (uint16_t)(nact > s.max_actions ? s.max_actions : nact);
+                b.traj_len[slot] = (uint32_t)depth;
+            }
+            collected++;
+        }
+        __threadfence_block();
+        __syncthreads();
+    }
+    if (l == 0) {
+        b.count[g] = collected;
+        b.forwards[g] = forwards;
+    }
+}
+
+// The net's index list: tree g's leaves take the net slots [offset[g], offset[g] + count[g]) in collection order, trees in
+// ascending order.  Also the counters: simulations grow by the forwards made, nn leaf evals by the leaves collected.
+__global__ __launch_bounds__(1024) void compact_batch_kernel(SearchDev s, LeafBatchDev b) {
+    __shared__ int wsum[16];
+    __shared__ int carry;
+    __shared__ unsigned long long fsum;
+    const int tid = threadIdx.x, l = tid & 63, w = tid >> 6;
+    if (tid == 0) {
+        carry = 0;
+        fsum = 0;
+    }
+    __syncthreads();
+    for (int chunk = 0; chunk < s.batch; chunk += 1024) {
+        const int g = chunk + tid;
+        const int c = g < s.batch ? b.count[g] : 0;
+        if (g < s.batch) atomicAdd(&fsum, (unsigned long long)b.forwards[g]);
+        const int incl = wave_incl_scan(c);
+        if (l == 63) wsum[w] = incl;
+        __syncthreads();
+        int off = carry;
+        for (int i = 0; i < w; i++) off += wsum[i];
+        if (g < s.batch) b.offset[g] = off + incl - c;
+        __syncthreads();
+        if (tid == 1023) carry = off + incl;
+        __threadfence_block();
+        __syncthreads();
+    }
+    const int slots = s.batch * b.leaves;
+    for (int i = tid; i < slots; i += 1024) {
+        const int g = i / b.leaves, j = i - g * b.leaves;
+        if (j < b.count[g]) b.index[b.offset[g] + j] = i;
+    }
+    if (tid == 0) {
+        *s.nn_count = carry;
+        s.counters[0] += fsum;
+        s.counters[1] += (unsigned long long)carry;
+    }
+}
+
+// Agent::policy_value_uncertainty outputs and softmax (policy.rs:10-19) of every collected leaf, one wave per slot: a leaf's
+// probabilities do not depend on the other leaves.  The arithmetic is expand_kernel's: the sum is the sequential f32 sum.
+template <int N>
+__global__ __launch_bounds__(64) void leaf_policy_kernel(SearchDev s, LeafBatchDev b, NetOut out) {
+    constexpr int NN = N * N;
+    const int slot = blockIdx.x, l = lane_id();
+    const int g = slot / b.leaves, j = slot - g * b.leaves;
+    if (j >= b.count[g]) return;
+    const int k = b.offset[g] + j;  // the leaf's slot in the net's outputs
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float* lg = reinterpret_cast<float*>(smem);
+    float* ex = lg + s.max_actions;
+    const int nact = b.nact[slot];
+    const uint16_t* acts = b.act + (size_t)slot * s.max_actions;
+    float value = 0.0f, variance = 0.0f;
+    if (s.agent_kind == TZ_AGENT_NET) {
+        value = out.value[k];
+        variance = out.variance[k];
+    } else if (s.agent_kind == TZ_AGENT_SIMPLE) {  // agent.rs:66-70
+        __shared__ tz_state le;
+        load_state(&le, &b.env[slot]);
+        __syncthreads();
+        const int fd = flat_diff<N>(&le) - s.half_komi / 2;
+        value = (float)fd / (float)NN;
+        if (le.to_move == 1) value = -value;
+    }
+    bool nan = false;
+    float mx = -3.4028235e38f;
+    for (int i = l; i < nact; i += 64) {
+        const int a = acts[i];
+        float x;
+        if (s.agent_kind == TZ_AGENT_NET) {
+            x = out.policy[((size_t)k * NN + (a % NN)) * out.policy_stride + a / NN];
+        } else if (s.agent_kind == TZ_AGENT_DUMMY) {
+            x = 1.0f;
+        } else {
+            const int ch = a / NN;
+            x = ch == 0 ? 4.0f : ch == 1 ? 2.0f : ch == 2 ? 3.0f : 1.0f;  // agent.rs:73-80
+        }
+        nan = nan || !(x == x);
+        lg[i] = x;
+        mx = x > mx ? x : mx;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const float o = __shfl_xor(mx, d);
+        mx = o > mx ? o : mx;
+    }
+    const bool bad = __any(nan) || !(value == value) || !(variance == variance);
+    if (bad) {
+        if (l == 0) {
+            atomicMax(s.error_flag, 7);
+            b.bad[slot] = 1;
+        }
+        return;
+    }
+    for (int i = l; i < nact; i += 64) ex[i] = tz_expf(lg[i] - mx);
+    __syncthreads();
+    float sum = 0.0f;
+    for (int i = 0; i < nact; i++) sum = sum + ex[i];
+    float* lo = b.logit + (size_t)slot * s.max_actions;
+    float* po = b.prob + (size_t)slot * s.max_actions;
+    for (int i = l; i < nact; i += 64) {
+        lo[i] = lg[i];
+        po[i] = ex[i] / sum;
+    }
+    if (l == 0) {
+        b.value[slot] = value;
+        b.variance[slot] = variance;
+        b.bad[slot] = 0;
+    }
+}
+
+// backward_network_eval (mcts.rs:171-225) for a tree's leaves strictly in collection order (mcts.rs:307-327): each backup changes
+// what the next one reads.  n of update_mean_value / update_standard_deviation is the node's visit_count now, which already holds
+// every forward of the round.  A leaf collected more than once in a round (always on a fresh root) has children from its first
+// expansion; the reference replaces `children` each time (mcts.rs:199-217), and since no forward of the round went below the leaf
+// the new children differ from the old only in the fields rewritten here, in the same slots.
+__global__ __launch_bounds__(64) void expand_batch_kernel(SearchDev s, LeafBatchDev b) {
+    const int g = blockIdx.x, l = lane_id();
+    __shared__ uint32_t tnode[TZ_MAX_DEPTH];
+    __shared__ uint32_t tvis[TZ_MAX_DEPTH];
+    const size_t base = slab_base(s, s.bank[g], g);
+    const int count = b.count[g];
+    for (int j = 0; j < count; j++) {
+        const size_t slot = (size_t)g * b.leaves + j;
+        if (b.bad[slot]) return;  // NaN from the agent: error 7 is set, the reference panics (mcts.rs:194)
+        const int len = (int)b.traj_len[slot];
+        for (int i = l; i < len; i += 64) {
+            const uint32_t nd = b.traj[slot * TZ_MAX_DEPTH + i];
+            tnode[i] = nd;
+            tvis[i] = s.t.visits[base + nd];
+        }
+        __syncthreads();
+        const int nact = b.nact[slot];
+        const uint16_t* acts = b.act + slot * s.max_actions;
+        const float* lg = b.logit + slot * s.max_actions;
+        const float* pr = b.prob + slot * s.max_actions;
+        const float value = b.value[slot], variance = b.variance[slot];
+        // leaf update, mcts.rs:190-196
+        const uint32_t leaf = tnode[len - 1];
+        const float n = (float)tvis[len - 1];
+        float mean = tz_bits_to_float(s.t.eval_bits[base + leaf]);
+        mean = mean + (-mean + value) / n;
+        float sd = s.t.std_dev[base + leaf];
+        sd = sd + (-sd + sqrtf(variance)) / n;
+        const bool again = s.t.nchild[base + leaf] != 0;  // expanded by an earlier leaf of this round
+        const uint32_t c0 = again ? s.t.child0[base + leaf] : s.alloc[g];
+        const bool full = !again && c0 + (uint32_t)nact > (uint32_t)s.cap;  // as expand_kernel
+        if (full && s.strict_capacity) {
+            if (l == 0) atomicMax(s.error_flag, 1);
+            return;
+        }
+        // children, node/mod.rs:66-79
+        const uint32_t child_bits = tz_float_to_bits(-mean);
+        for (int i = l; i < (full ? 0 : nact); i += 64) {
+            const size_t ci = base + c0 + i;
+            s.t.eval_tag[ci] = TZ_EVAL_VALUE;
+            s.t.eval_bits[ci] = child_bits;
+            s.t.visits[ci] = 0;
+            s.t.prob[ci] = pr[i];
+            s.t.logit[ci] = lg[i];
+            s.t.std_dev[ci] = sd;
+            if (!again) {
+                s.t.child0[ci] = 0;
+                s.t.nchild[ci] = 0;
+                s.t.action[ci] = acts[i];
+            }
+        }
+        if (l == 0) {
+            s.t.eval_bits[base + leaf] = tz_float_to_bits(mean);
+            s.t.std_dev[base + leaf] = sd;
+            if (full) {
+                atomicAdd(&s.counters[2], 1ull);
+            } else if (!again) {
+                s.alloc[g] = c0 + (uint32_t)nact;
+                s.t.child0[base + leaf] = c0;
+                s.t.nchild[base + leaf] = (uint16_t)nact;
+            }
+        }
+        __syncthreads();
+        backup(s, base, tnode, tvis, len - 1, ev_value(value * TZ_DISCOUNT), variance * TZ_DISCOUNT * TZ_DISCOUNT, ev_value(mean));
+        __threadfence_block();
+        __syncthreads();
+    }
+}
+
 // noise.rs:10-26 with the sample supplied by the caller
 __global__ __launch_bounds__(64) void noise_kernel(SearchDev s, const float* noise, int amax, float ratio) {
     const int g = blockIdx.x, l = lane_id();
@@ -557,18 +806,12 @@ __global__ __launch_bounds__(64) void node_kernel(SearchDev s, int g, const uint
     }
 }
 
-// Node::select_best_action, node/mod.rs:132-161
-__global__ __launch_bounds__(64) void select_best_kernel(SearchDev s, uint16_t* out) {
-    const int g = blockIdx.x, l = lane_id();
-    const size_t base = slab_base(s, s.bank[g], g);
-    const int nc = s.t.nchild[base];
-    const uint32_t c0 = s.t.child0[base];
-    if (nc == 0) {
-        if (l == 0) out[g] = 0xFFFF;
-        return;
-    }
+// Node::select_best_action, node/mod.rs:132-161, of the node at slab index `node` (base + index) with children [c0, c0 + nc), nc > 0:
+// the position of the chosen child among them (uniform over the wave)
+__device__ __forceinline__ int select_best_child(const SearchDev& s, size_t base, size_t node, uint32_t c0, int nc) {
+    const int l = lane_id();
     int pick;
-    if (s.t.eval_tag[base] != TZ_EVAL_VALUE) {  // solved: first minimum child evaluation
+    if (s.t.eval_tag[node] != TZ_EVAL_VALUE) {  // solved: first minimum child evaluation
         Ev best{0, 0};
         int best_i = 0x7fffffff;
         for (int i = l; i < nc; i += 64) {
@@ -625,7 +868,40 @@ __global__ __launch_bounds__(64) void select_best_kernel(SearchDev s, uint16_t* 
         }
         pick = bv == 0 ? bpi : bvi;
     }
+    return pick;
+}
+
+__global__ __launch_bounds__(64) void select_best_kernel(SearchDev s, uint16_t* out) {
+    const int g = blockIdx.x, l = lane_id();
+    const size_t base = slab_base(s, s.bank[g], g);
+    const int nc = s.t.nchild[base];
+    const uint32_t c0 = s.t.child0[base];
+    if (nc == 0) {
+        if (l == 0) out[g] = 0xFFFF;
+        return;
+    }
+    const int pick = select_best_child(s, base, base, c0, nc);
     if (l == 0) out[g] = s.t.action[base + c0 + pick];
+}
+
+// Node::principal_variation, node/mod.rs:40-62, 87-90: one wave follows select_best_action from game g's root until a node
+// needs initialisation or is terminal.  moves[cap] receives the first cap moves, *len the whole length.
+__global__ __launch_bounds__(64) void principal_variation_kernel(SearchDev s, int g, uint16_t* moves, int cap, int* len) {
+    const int l = lane_id();
+    const size_t base = slab_base(s, s.bank[g], g);
+    size_t node = base;
+    int d = 0;
+    for (; d < TZ_MAX_DEPTH; d++) {
+        const int nc = s.t.nchild[node];
+        const bool known = s.t.eval_tag[node] != TZ_EVAL_VALUE;
+        if ((nc == 0 && !known) || (known && s.t.eval_bits[node] == 0)) break;
+        if (nc == 0) break;  // a solved node whose children the tree does not hold: the reference would panic (mod.rs:139)
+        const uint32_t c0 = s.t.child0[node];
+        const int pick = select_best_child(s, base, node, c0, nc);
+        node = base + c0 + pick;
+        if (l == 0 && d < cap) moves[d] = s.t.action[node];
+    }
+    if (l == 0) *len = d;
 }
 
 __device__ __forceinline__ void copy_node(const SearchDev& s, size_t dst, size_t src) {
@@ -962,6 +1238,29 @@ int tz_tree_set_start_children(const SearchDev& s, const int32_t* child_index_de
 }
 int tz_tree_gumbel_root_fixup(const SearchDev& s, hipStream_t st) {
     gumbel_fixup_kernel<<<s.batch, 64, 0, st>>>(s);
+    TZ_LAUNCH_CHECK();
+    return TZ_OK;
+}
+int tz_tree_principal_variation(const SearchDev& s, int game, uint16_t* moves_dev, int cap, int* len_dev, hipStream_t st) {
+    principal_variation_kernel<<<1, 64, 0, st>>>(s, game, moves_dev, cap, len_dev);
+    TZ_LAUNCH_CHECK();
+    return TZ_OK;
+}
+int tz_tree_descend_batch(const SearchDev& s, const LeafBatchDev& b, hipStream_t st) {
+    TZ_DISPATCH_N(s.n, (descend_batch_kernel<NB><<<s.batch, 64, 0, st>>>(s, b)));
+    TZ_LAUNCH_CHECK();
+    return TZ_OK;
+}
+int tz_tree_compact_batch(const SearchDev& s, const LeafBatchDev& b, hipStream_t st) {
+    compact_batch_kernel<<<1, 1024, 0, st>>>(s, b);
+    TZ_LAUNCH_CHECK();
+    return TZ_OK;
+}
+int tz_tree_expand_batch(const SearchDev& s, const LeafBatchDev& b, const NetOut& out, hipStream_t st) {
+    const size_t smem = 2 * (size_t)s.max_actions * sizeof(float);
+    TZ_DISPATCH_N(s.n, (leaf_policy_kernel<NB><<<s.batch * b.leaves, 64, smem, st>>>(s, b, out)));
+    TZ_LAUNCH_CHECK();
+    expand_batch_kernel<<<s.batch, 64, 0, st>>>(s, b);
     TZ_LAUNCH_CHECK();
     return TZ_OK;
 }
