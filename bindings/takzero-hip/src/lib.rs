@@ -187,6 +187,16 @@ impl<const B: usize> HipBatchedMCTS<B> {
     pub fn simulate_batch(&mut self, betas: &[f32], leaves: usize, rounds: usize) {
         check(unsafe { sys::tz_search_simulate_batch(self.raw, betas.as_ptr(), leaves as i32, rounds as i32) }).unwrap();
     }
+    /// The in-tree selection rule of Node::forward for every later simulation on this handle: sys::TZ_SELECT_PUCT (policy.rs:78-95,
+    /// the default), sys::TZ_SELECT_UCT (:104-117) or sys::TZ_SELECT_IMPROVED (:57-69).  The reference edits mcts.rs:132 instead.
+    pub fn set_selection(&mut self, rule: i32) -> Result<(), TchError> {
+        check(unsafe { sys::tz_search_set_selection(self.raw, rule) })
+    }
+    pub fn selection(&self) -> i32 {
+        let mut rule = 0i32;
+        check(unsafe { sys::tz_search_get_selection(self.raw, &mut rule) }).unwrap();
+        rule
+    }
     /// Node::principal_variation (node/mod.rs:40-62, 87-90) of one root, as move indices
     pub fn principal_variation(&self, game: usize) -> Vec<u16> {
         let mut out = vec![0u16; 512];

@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "selection_arg.h"
 #include "takzero_hip.h"
 
 #define CHECK(call)                                                        \
@@ -35,9 +36,14 @@ static std::string eval_text(uint8_t tag, uint32_t bits) {
 }
 
 int main(int argc, char** argv) {
-    std::string model, tps;
+    std::string model, tps, selection = "puct";
     int arch = TZ_ARCH_NET5, n = 5, blocks = 0, leaves = 128, rounds = 8, precision = TZ_PREC_F16, device = 0, half_komi = 4, show = 10;
     unsigned long long seed = 0;
+    auto usage = []() {
+        fprintf(stderr, "usage: analysis_cli [--model FILE.ot|.tzw --tps TPS --arch 4|5|6|100 --n N --blocks K --leaves 128 --rounds 8 --selection puct|uct|improved "
+                        "--half-komi 4 --children 10 --seed X --device G --f32|--bf16]\n");
+        return 2;
+    };
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return i + 1 < argc ? argv[++i] : ""; };
@@ -47,6 +53,7 @@ int main(int argc, char** argv) {
         else if (a == "--n") n = atoi(next());
         else if (a == "--blocks") blocks = atoi(next());
         else if (a == "--leaves") leaves = atoi(next());
+        else if (a == "--selection") selection = next();
         else if (a == "--rounds") rounds = atoi(next());
         else if (a == "--half-komi") half_komi = atoi(next());
         else if (a == "--children") show = atoi(next());
@@ -54,12 +61,9 @@ int main(int argc, char** argv) {
         else if (a == "--device") device = atoi(next());
         else if (a == "--f32") precision = TZ_PREC_F32;
         else if (a == "--bf16") precision = TZ_PREC_BF16;
-        else {
-            fprintf(stderr, "usage: analysis_cli [--model FILE.ot|.tzw --tps TPS --arch 4|5|6|100 --n N --blocks K --leaves 128 --rounds 8 "
-                            "--half-komi 4 --children 10 --seed X --device G --f32|--bf16]\n");
-            return 2;
-        }
+        else return usage();
     }
+    if (selection_rule(selection) < 0) return usage();
     if (arch == TZ_ARCH_NET5) n = 5;
     if (arch == TZ_ARCH_NET4_SIMHASH) n = 4;
     if (arch == TZ_ARCH_NET6_SIMHASH) n = 6;
@@ -69,6 +73,7 @@ int main(int argc, char** argv) {
     if (!model.empty()) CHECK(tz_net_load_weights(net, model.c_str()));
     else CHECK(tz_net_init_random(net, seed));
     CHECK(tz_search_create(net, TZ_AGENT_NET, 1, n, half_komi, 0, &search));
+    CHECK(tz_search_set_selection(search, selection_rule(selection)));
     if (!tps.empty()) {
         tz_state start;
         const int32_t game = 0;

@@ -15,6 +15,7 @@
 #include <future>
 #include <string>
 
+#include "selection_arg.h"
 #include "takzero_hip.h"
 
 struct Reload {
@@ -93,7 +94,7 @@ static int reload_model(void* user) {
     } while (0)
 
 int main(int argc, char** argv) {
-    std::string directory, model, search = "gumbel", watch = "model_latest.ot";
+    std::string directory, model, search = "gumbel", selection = "puct", watch = "model_latest.ot";
     int arch = TZ_ARCH_NET5, n = 5, blocks = 0, games = 128, sims = 768, iterations = -1, k = 64, precision = TZ_PREC_F16;
     int rank = 0, world = 1, device = -1, min_positions = 0;
     unsigned long long seed = 0;
@@ -107,6 +108,7 @@ int main(int argc, char** argv) {
         else if (a == "--watch") watch = next();
         else if (a == "--async-reload") async_reload = true;
         else if (a == "--search") search = next();
+        else if (a == "--selection") selection = next();
         else if (a == "--arch") arch = atoi(next());
         else if (a == "--n") n = atoi(next());
         else if (a == "--blocks") blocks = atoi(next());
@@ -129,9 +131,9 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
-    if (directory.empty()) {
+    if (directory.empty() || selection_rule(selection) < 0) {
         fprintf(stderr, "usage: reanalyze_cli --directory DIR [--model FILE --watch model_latest.ot --arch 4|5|6|100 --n N --blocks K --games B "
-                        "--sims S --search puct|gumbel --sampled-actions K --iterations I --min-positions P --wait-limit SECONDS --seed X "
+                        "--sims S --search puct|gumbel --selection puct|uct|improved --sampled-actions K --iterations I --min-positions P --wait-limit SECONDS --seed X "
                         "--rank R --world N --device G --async-reload --bf16|--f16c6|--f16c8|--f16x2]\n");
         return 2;
     }
@@ -146,6 +148,7 @@ int main(int argc, char** argv) {
     if (!model.empty()) CHECK(tz_net_load_weights(net, model.c_str()));
     else CHECK(tz_net_init_random(net, seed));
     CHECK(tz_search_create(net, TZ_AGENT_NET, games, n, 4, 0, &mcts));
+    CHECK(tz_search_set_selection(mcts, selection_rule(selection)));      // the native driver runs on the handle's rule
     CHECK(tz_reanalyze_create(mcts, sims, seed, rank, world, search == "puct" ? 0 : 1, k, &ra));
     Reload reload{net, directory + "/" + watch};
     reload.async = async_reload;

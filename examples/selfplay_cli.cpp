@@ -18,6 +18,7 @@
 #include <future>
 #include <string>
 
+#include "selection_arg.h"
 #include "takzero_hip.h"
 
 struct Reload {
@@ -99,7 +100,7 @@ static int reload_model(void* user) {
     } while (0)
 
 int main(int argc, char** argv) {
-    std::string directory, model, search = "gumbel", watch = "model_latest.ot", comm_kind, comm_dir;
+    std::string directory, model, search = "gumbel", selection = "puct", watch = "model_latest.ot", comm_kind, comm_dir;
     int arch = TZ_ARCH_NET5, n = 5, blocks = 0, games = 128, sims = 768, moves = -1, exploration = 0, k = 64, precision = TZ_PREC_F16;
     bool async_reload = false;
     int rank = 0, world = 1, device = -1;
@@ -111,6 +112,7 @@ int main(int argc, char** argv) {
         if (a == "--directory") directory = next();
         else if (a == "--model") model = next();
         else if (a == "--search") search = next();
+        else if (a == "--selection") selection = next();
         else if (a == "--arch") arch = atoi(next());
         else if (a == "--n") n = atoi(next());
         else if (a == "--blocks") blocks = atoi(next());
@@ -138,9 +140,9 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
-    if (directory.empty() || (world > 1 && comm_kind != "rccl" && comm_kind != "fs")) {
+    if (directory.empty() || selection_rule(selection) < 0 || (world > 1 && comm_kind != "rccl" && comm_kind != "fs")) {
         fprintf(stderr, "usage: selfplay_cli --directory DIR [--model FILE.ot|.tzw --watch model_latest.ot --arch 4|5|6|100 --n N --blocks K "
-                        "--games B --sims S --search puct|gumbel --sampled-actions K --moves M --exploration --async-reload --f16|--bf16|--f16c6|--f16c8|--f16x2 "
+                        "--games B --sims S --search puct|gumbel --selection puct|uct|improved --sampled-actions K --moves M --exploration --async-reload --f16|--bf16|--f16c6|--f16c8|--f16x2 "
                         "--wait-limit SECONDS --seed X] [--rank R --world N --comm rccl|fs --comm-dir D --device G]\n");
         return 2;
     }
@@ -157,6 +159,7 @@ int main(int argc, char** argv) {
     if (!model.empty()) CHECK(tz_net_load_weights(net, model.c_str()));
     else CHECK(tz_net_init_random(net, seed));      // Net::new(DEVICE, seed), selfplay/src/main.rs:71 (same seed on every rank)
     CHECK(tz_search_create(net, TZ_AGENT_NET, games, n, 4, 0, &mcts));
+    CHECK(tz_search_set_selection(mcts, selection_rule(selection)));      // the native driver runs on the handle's rule
     CHECK(tz_selfplay_create(mcts, sims, seed, rank, search == "puct" ? 0 : 1, k, exploration, &sp));
     if (world > 1) {
         if (comm_kind == "rccl") {

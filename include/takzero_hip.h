@@ -226,6 +226,24 @@ int tz_search_simulate(tz_search* s, const float* betas, int n_sims);
  * read it (the code that would is commented out, node/mod.rs:115-122) and it is back at zero after every call. */
 #define TZ_SIMULATE_BATCH_MAX_SLOTS 16384
 int tz_search_simulate_batch(tz_search* s, const float* betas, int leaves, int rounds);
+/* The in-tree selection rule of Node::forward (mcts.rs:107-138).  The reference picks one by editing mcts.rs:132; here it is a
+ * switch on the handle, read by tz_search_simulate, tz_search_simulate_batch, tz_search_gumbel_sh (below the sampled root child;
+ * halving at the root is unchanged) and every native driver that runs on the handle (tz_selfplay_*, tz_reanalyze_*, tz_compete,
+ * tz_puzzle_benchmark).  All three rules skip a winning child unless the parent is a proven loss, and break ties towards the
+ * last child (Iterator::max_by_key). */
+#define TZ_SELECT_PUCT 0     /* select_with_puct, policy.rs:78-95 with :140-156; the default */
+#define TZ_SELECT_UCT 1      /* select_with_uct, policy.rs:104-117 with upper_confidence_bound :158-164: q + sqrt(ln N / n) +
+                              * std_dev * beta.  An unvisited child scores +inf, so they are visited from the last to the first */
+#define TZ_SELECT_IMPROVED 2 /* select_with_improved_policy, policy.rs:57-69 with improved_policy :36-48 and sigma_improve
+                              * :131-138 (the non-root rule of Gumbel MuZero): softmax(completed q * sqrt(max visits) + logit) -
+                              * n / (N + 1).  beta is not read */
+/* Sets the rule.  Allowed at any time between calls: synchronises the handle's stream and drops its captured simulation graphs,
+ * so the next simulations run (and are captured again) with the new rule.  TZ_EINVAL for an unknown rule; the rule then stays.
+ * A NaN score (the reference's NotNan panics, policy.rs:113) surfaces as TZ_ENUMERIC from the simulate call.
+ * With TZ_SELECT_IMPROVED and a full node pool (tz_search_pool_overflows), a leaf that was evaluated but not expanded counts as
+ * needing initialisation, so its completed value is its parent's evaluation; the reference's trees have no such state. */
+int tz_search_set_selection(tz_search* s, int rule);
+int tz_search_get_selection(tz_search* s, int* rule_out);
 /* Where the rounds of tz_search_simulate_batch spent their time since profiling was switched on (tz_search_profile with reset 1;
  * reset 1 or 2 also clears these): HIP-event time in ms of the forward kernel with the compaction, of the network call, and of
  * the backward pass with the leaf softmax, summed over `rounds` rounds.  Any pointer may be NULL. */

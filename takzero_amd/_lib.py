@@ -42,6 +42,7 @@ SYMBOLS = [
     "tz_trainer_load", "tz_trainer_save", "tz_trainer_load_weights_mem", "tz_trainer_get_extras", "tz_trainer_from_net", "tz_trainer_to_net", "tz_learn_set_save_points",
     "tz_learn_create", "tz_learn_destroy", "tz_learn_feed", "tz_learn_add_lines", "tz_learn_buffer_len", "tz_learn_step", "tz_learn_run", "tz_learn_last_batch",
     "tz_search_simulate_batch", "tz_search_principal_variation", "tz_search_batch_profile",
+    "tz_search_set_selection", "tz_search_get_selection",
 ]
 
 _lib = None
@@ -119,6 +120,8 @@ def load():
     lib.tz_search_simulate.argtypes = [vp, vp, ci]
     lib.tz_search_simulate_batch.argtypes = [vp, vp, ci, ci]
     lib.tz_search_batch_profile.argtypes = [vp] + [C.POINTER(C.c_double)] * 3 + [C.POINTER(C.c_uint64)]
+    lib.tz_search_set_selection.argtypes = [vp, ci]
+    lib.tz_search_get_selection.argtypes = [vp, C.POINTER(ci)]
     lib.tz_search_principal_variation.argtypes = [vp, ci, vp, ci, C.POINTER(ci)]
     lib.tz_search_apply_noise.argtypes = [vp, vp, ci, cf]
     lib.tz_search_root_info.argtypes = [vp, vp]

@@ -29,6 +29,9 @@ PREC_NAMES = {"bf16": PREC_BF16, "f16": PREC_F16, "f32": PREC_F32, "f16x2": PREC
 PREC_DEFAULT = PREC_NAMES[os.environ.get("TZ_PRECISION", "f16")]
 AGENT_NET, AGENT_DUMMY, AGENT_SIMPLE = 0, 1, 2
 EVAL_VALUE, EVAL_WIN, EVAL_LOSS, EVAL_DRAW = 0, 1, 2, 3
+# in-tree selection of Node::forward: select_with_puct / select_with_uct / select_with_improved_policy (policy.rs:78-95, 104-117, 57-69)
+SELECT_PUCT, SELECT_UCT, SELECT_IMPROVED = 0, 1, 2
+SELECT_NAMES = {"puct": SELECT_PUCT, "uct": SELECT_UCT, "improved": SELECT_IMPROVED}
 TERMINAL_NONE, TERMINAL_WIN, TERMINAL_LOSS, TERMINAL_DRAW = -1, 0, 1, 2
 DISCOUNT_FACTOR = np.float32(0.997)  # search/mod.rs:7
 
@@ -283,6 +286,21 @@ class BatchedMCTS:
         b = np.ascontiguousarray(betas, dtype=np.float32)
         assert b.shape == (self.batch,)
         check(self.lib.tz_search_simulate_batch(self.h, b.ctypes.data, leaves, rounds))
+
+    def set_selection(self, rule):
+        """The in-tree selection rule of every later simulation on this handle (lock-step, simulate_batch, and Gumbel halving
+        below the sampled root child): "puct" (the default), "uct" or "improved", or one of the SELECT_* constants."""
+        if isinstance(rule, str):
+            if rule not in SELECT_NAMES:
+                raise TakzeroError(-1, "unknown selection rule %r (puct, uct, improved)" % (rule,))
+            rule = SELECT_NAMES[rule]
+        check(self.lib.tz_search_set_selection(self.h, int(rule)))
+
+    @property
+    def selection(self):
+        r = C.c_int(-1)
+        check(self.lib.tz_search_get_selection(self.h, C.byref(r)))
+        return {v: k for k, v in SELECT_NAMES.items()}[r.value]
 
     def apply_noise(self, noise, ratio):
         nz = np.ascontiguousarray(noise, dtype=np.float32)

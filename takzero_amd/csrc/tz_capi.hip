@@ -71,6 +71,7 @@ int check_error_flag(tz_search* s) {
         case 4: return tz_fail(TZ_ESTATE, "search: no child eligible for selection (policy.rs:94 expect)");
         case 6: return tz_fail(TZ_ESTATE, "search: noise applied to an un-expanded root (noise.rs:12-15 assert)");
         case 7: return tz_fail(TZ_ENUMERIC, "search: the network produced NaN (net5.rs:263 / mcts.rs:194 expect)");
+        case 8: return tz_fail(TZ_ENUMERIC, "search: a selection score is NaN (policy.rs:113 NotNan)");
         default: return tz_fail(TZ_EDEVICE, "search: unknown device error flag");
     }
 }
@@ -305,6 +306,7 @@ int tz_search_create(tz_net* net, int agent_kind, int batch, int board_n, int ha
     d.strict_capacity = getenv("TZ_STRICT_CAPACITY") != nullptr;
     d.max_actions = default_max_actions(board_n);
     d.agent_kind = agent_kind;
+    d.select_rule = TZ_SELECT_PUCT;
     const size_t nodes = (size_t)2 * batch * d.cap;
     int rc = 0;
     rc |= dev_alloc(&d.t.eval_tag, nodes);
@@ -451,6 +453,28 @@ int tz_search_simulate_batch(tz_search* s, const float* betas, int leaves, int r
     rc = check_error_flag(s);
     drain_batch_profile(s);
     return rc;
+}
+
+int tz_search_set_selection(tz_search* s, int rule) {
+    if (!s) return tz_fail(TZ_EINVAL, "tz_search_set_selection: null argument");
+    if (rule != TZ_SELECT_PUCT && rule != TZ_SELECT_UCT && rule != TZ_SELECT_IMPROVED)
+        return tz_fail(TZ_EINVAL, "tz_search_set_selection: unknown selection rule");
+    TZ_HIP(hipSetDevice(s->device));
+    TZ_HIP(hipStreamSynchronize(s->stream));
+    // the captured simulations hold the descend kernel of the old rule
+    for (int i = 0; i < 2; i++) {
+        if (s->graph[i]) (void)hipGraphExecDestroy(s->graph[i]);
+        s->graph[i] = nullptr;
+        s->warm[i] = 0;
+    }
+    s->d.select_rule = rule;
+    return TZ_OK;
+}
+
+int tz_search_get_selection(tz_search* s, int* rule_out) {
+    if (!s || !rule_out) return tz_fail(TZ_EINVAL, "tz_search_get_selection: null argument");
+    *rule_out = s->d.select_rule;
+    return TZ_OK;
 }
 
 int tz_search_batch_profile(tz_search* s, double* forward_ms, double* net_ms, double* backward_ms, uint64_t* rounds) {

@@ -1,7 +1,8 @@
 // tz_tree.hip — batched MCTS on the device: one wavefront per game.
 //
 // Replaces, for B concurrent games stepped in lock-step (takzero/src/search/node/batched.rs:63-128):
-//   Node::forward            mcts.rs:107-138   -> descend_kernel   (select with PUCT policy.rs:78-95)
+//   Node::forward            mcts.rs:107-138   -> descend_kernel   (select with PUCT policy.rs:78-95, UCT :104-117 or the
+//                                                  improved policy :57-69, by SearchDev::select_rule)
 //   Node::backward_known_eval mcts.rs:141-163  -> descend_kernel   (immediately, as batched.rs:78-82)
 //   softmax + backward_network_eval policy.rs:10-19, mcts.rs:171-225 -> expand_kernel
 //   propagate_child_eval / node_solver mcts.rs:49-102 -> backup()
@@ -176,12 +177,28 @@ __device__ void backup(const SearchDev& s, size_t base, const uint32_t* tnode, c
 }
 
 // ---------------------------------------------------------------------------------------------
+// Floats in the LDS row of the IMPROVED pass of forward_walk: one per child at the default max_actions, none for the other rules.
+template <int N, int RULE>
+struct SelectRow {
+    static constexpr int LEN = RULE == TZ_SELECT_IMPROVED ? (N <= 5 ? TZ_MAX_ACTIONS : TZ_MAX_ACTIONS_6) : 0;
+};
+
+// ---------------------------------------------------------------------------------------------
 // Node::forward, mcts.rs:107-138, from `node` with env at that node's position: the walk shared by descend_kernel (one forward per
 // launch) and descend_batch_kernel (a round of forwards per launch).  Records the path in tnode/tvis (LDS), leaves env at the leaf's
 // position.  Returns 0 Known (in `known`), 1 NeedsNetwork, 2 error (flag set); depth = nodes on the path.
-template <int N>
+//
+// RULE picks the in-tree selection at compile time (the reference switches it by editing mcts.rs:132): TZ_SELECT_PUCT
+// policy.rs:78-95, TZ_SELECT_UCT policy.rs:104-117, TZ_SELECT_IMPROVED policy.rs:57-69.  All three filter with
+// `parent.is_loss() || !child.is_win()` and break ties towards the last index (Iterator::max_by_key).  prow is the LDS row of the
+// IMPROVED pass (SelectRow<N, RULE>::LEN floats) and nullptr in the other instantiations.
+//
+// IMPROVED and a full node pool: a leaf that was evaluated but not expanded (expand_kernel, non-strict capacity) has no
+// children and no known evaluation, so the completion below treats it as needs_initialization() and gives it the parent's
+// evaluation although it has been visited.  The reference's heap trees have no such state.
+template <int N, int RULE>
 __device__ __forceinline__ int forward_walk(const SearchDev& s, size_t base, tz_state& env, uint32_t* tnode, uint32_t* tvis,
-                                            uint32_t node, float beta, int& depth, Ev& known) {
+                                            uint32_t node, float beta, int& depth, Ev& known, float* prow) {
     const int l = lane_id();
     for (;;) {
         const uint32_t vis = s.t.visits[base + node] + 1;
@@ -214,24 +231,114 @@ __device__ __forceinline__ int forward_walk(const SearchDev& s, size_t base, tz_
             if (l == 0) atomicMax(s.error_flag, 2);
             return 2;
         }
-        // select_with_puct, policy.rs:78-95 (ties -> last index: Iterator::max_by_key)
+        // the selection rule (ties -> last index: Iterator::max_by_key)
         const uint32_t c0 = s.t.child0[base + node];
         const float parent = (float)vis;
-        const float er = tz_logf(((1.0f + parent) + 500.0f) / 500.0f) + 4.0f;  // policy.rs:143-145
-        const float sq = sqrtf(parent);
         const bool parent_loss = ev.tag == TZ_EVAL_LOSS;
         float best_score = 0.0f;
         int best_i = -1;
-        for (int i = l; i < nc; i += 64) {
-            const size_t ci = base + c0 + i;
-            const Ev ce{s.t.eval_tag[ci], s.t.eval_bits[ci]};
-            if (!(parent_loss || ce.tag != TZ_EVAL_WIN)) continue;
-            const float q = ev_to_notnan(ev_negate(ce));
-            const float puct = ((er * s.t.prob[ci]) * sq) / (1.0f + (float)s.t.visits[ci]);
-            const float score = (q + puct) + s.t.std_dev[ci] * beta;
-            if (best_i < 0 || !(score < best_score)) {
-                best_score = score;
-                best_i = i;
+        if constexpr (RULE == TZ_SELECT_PUCT) {
+            // select_with_puct, policy.rs:78-95
+            const float er = tz_logf(((1.0f + parent) + 500.0f) / 500.0f) + 4.0f;  // policy.rs:143-145
+            const float sq = sqrtf(parent);
+            for (int i = l; i < nc; i += 64) {
+                const size_t ci = base + c0 + i;
+                const Ev ce{s.t.eval_tag[ci], s.t.eval_bits[ci]};
+                if (!(parent_loss || ce.tag != TZ_EVAL_WIN)) continue;
+                const float q = ev_to_notnan(ev_negate(ce));
+                const float puct = ((er * s.t.prob[ci]) * sq) / (1.0f + (float)s.t.visits[ci]);
+                const float score = (q + puct) + s.t.std_dev[ci] * beta;
+                if (best_i < 0 || !(score < best_score)) {
+                    best_score = score;
+                    best_i = i;
+                }
+            }
+        } else if constexpr (RULE == TZ_SELECT_UCT) {
+            // select_with_uct, policy.rs:104-117.  A node with children has vis >= 2, so ln > 0 and an unvisited child scores
+            // ln(N) / 0 = +inf: those are taken from the last index to the first.
+            const float lnp = tz_logf(parent);
+            bool nan = false;
+            for (int i = l; i < nc; i += 64) {
+                const size_t ci = base + c0 + i;
+                const Ev ce{s.t.eval_tag[ci], s.t.eval_bits[ci]};
+                if (!(parent_loss || ce.tag != TZ_EVAL_WIN)) continue;
+                const float q = ev_to_notnan(ev_negate(ce));
+                const float uct = 1.0f * sqrtf(lnp / (float)s.t.visits[ci]);  // policy.rs:158-164
+                const float score = (q + uct) + s.t.std_dev[ci] * beta;
+                nan = nan || !(score == score);
+                if (best_i < 0 || !(score < best_score)) {
+                    best_score = score;
+                    best_i = i;
+                }
+            }
+            if (__any(nan)) {  // NotNan::new panics, policy.rs:113
+                if (l == 0) atomicMax(s.error_flag, 8);
+                return 2;
+            }
+        } else {
+            // select_with_improved_policy, policy.rs:57-69; beta is not read
+            // The row holds a default max_actions, so this is a pure guard: a node with more children was expanded under a larger
+            // max_actions than the row allows.  Flag 3 is the one gen_moves raises for a position with more legal moves than
+            // max_actions, and the host words it that way.
+            if (nc > SelectRow<N, RULE>::LEN) {
+                if (l == 0) atomicMax(s.error_flag, 3);
+                return 2;
+            }
+            uint32_t vm = 0;  // most_visited_count, policy.rs:23-29
+            for (int i = l; i < nc; i += 64) {
+                const uint32_t v = s.t.visits[base + c0 + i];
+                vm = v > vm ? v : vm;
+            }
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+                const uint32_t o = (uint32_t)__shfl_xor((int)vm, d);
+                vm = o > vm ? o : vm;
+            }
+            const float sqv = sqrtf((float)vm);
+            // improved_policy, policy.rs:36-48: p = sigma_improve(completed, std_dev, 0.0, vmax) + logit over every child
+            bool nan = false;
+            float mx = -3.4028235e38f;
+            for (int i = l; i < nc; i += 64) {
+                const size_t ci = base + c0 + i;
+                const Ev ce{s.t.eval_tag[ci], s.t.eval_bits[ci]};
+                const bool needs_init = s.t.nchild[ci] == 0 && !ev_known(ce);
+                // The reference's `.into()` here is From<Eval> for NotNan<f32> (ev_to_notnan); ev_to_f32 gives the same bits:
+                // the two differ only for a Value, which ev_to_f32 multiplies by powif(d, 0) == 1.0f, and 1.0f * x == x.
+                const float completed = ev_to_f32(needs_init ? ev : ev_negate(ce));
+                const float p = ((completed + s.t.std_dev[ci] * 0.0f) * sqv) + s.t.logit[ci];  // policy.rs:131-138
+                nan = nan || !(p == p);
+                prow[i] = p;
+                mx = p > mx ? p : mx;
+            }
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+                const float o = __shfl_xor(mx, d);
+                mx = o > mx ? o : mx;
+            }
+            if (__any(nan)) {  // NotNan, policy.rs:37
+                if (l == 0) atomicMax(s.error_flag, 8);
+                return 2;
+            }
+            // softmax, policy.rs:10-19: each lane rewrites the slots it wrote; the sum is the sequential f32 sum in child order,
+            // read from LDS by every lane (same address: a broadcast), as in expand_kernel
+            for (int i = l; i < nc; i += 64) prow[i] = tz_expf(prow[i] - mx);
+            __syncthreads();
+            float sum = 0.0f;
+            for (int i = 0; i < nc; i++) sum = sum + prow[i];
+            const float denom = (float)(vis + 1u);  // (self.visit_count + 1) as f32, policy.rs:65
+            for (int i = l; i < nc; i += 64) {
+                const size_t ci = base + c0 + i;
+                if (!(parent_loss || s.t.eval_tag[ci] != TZ_EVAL_WIN)) continue;
+                const float score = prow[i] / sum - (float)s.t.visits[ci] / denom;
+                nan = nan || !(score == score);
+                if (best_i < 0 || !(score < best_score)) {
+                    best_score = score;
+                    best_i = i;
+                }
+            }
+            if (__any(nan)) {
+                if (l == 0) atomicMax(s.error_flag, 8);
+                return 2;
             }
         }
 #pragma unroll
@@ -253,7 +360,7 @@ __device__ __forceinline__ int forward_walk(const SearchDev& s, size_t base, tz_
     }
 }
 
-template <int N>
+template <int N, int RULE>
 __global__ __launch_bounds__(64) void descend_kernel(SearchDev s, int from_start) {
     constexpr int NN = N * N;
     const int g = blockIdx.x, l = lane_id();
@@ -261,6 +368,11 @@ __global__ __launch_bounds__(64) void descend_kernel(SearchDev s, int from_start
     __shared__ uint32_t tnode[TZ_MAX_DEPTH];
     __shared__ uint32_t tvis[TZ_MAX_DEPTH];
     __shared__ uint8_t reach[NN * 4];
+    float* prow = nullptr;
+    if constexpr (RULE == TZ_SELECT_IMPROVED) {
+        __shared__ float row[SelectRow<N, RULE>::LEN];
+        prow = row;
+    }
     load_state(&env, &s.env[g]);
     const size_t base = slab_base(s, s.bank[g], g);
     uint32_t node = 0;
@@ -276,7 +388,7 @@ __global__ __launch_bounds__(64) void descend_kernel(SearchDev s, int from_start
     }
     int depth = 0;
     Ev known{0, 0};
-    const int kind = forward_walk<N>(s, base, env, tnode, tvis, node, beta, depth, known);  // 0 known, 1 needs network, 2 error
+    const int kind = forward_walk<N, RULE>(s, base, env, tnode, tvis, node, beta, depth, known, prow);  // 0 known, 1 needs network, 2 error
     __syncthreads();
     if (kind == 0) {
         // backward_known_eval, mcts.rs:141-163: the leaf itself is not updated
@@ -456,7 +568,7 @@ __global__ __launch_bounds__(64) void expand_kernel(SearchDev s, NetOut out) {
 // One wave per tree runs the forward loop of mcts.rs:281-300: up to 4 * leaves forwards, a Known result backed up at once (:284),
 // a leaf that needs the network written to the tree's next slot, until `leaves` are collected (:297).  A forward reads the visit
 // counts and solver results lane 0 stored in the forwards before it, hence the fence and barrier between trajectories.
-template <int N>
+template <int N, int RULE>
 __global__ __launch_bounds__(64) void descend_batch_kernel(SearchDev s, LeafBatchDev b) {
     constexpr int NN = N * N;
     const int g = blockIdx.x, l = lane_id();
@@ -465,6 +577,11 @@ __global__ __launch_bounds__(64) void descend_batch_kernel(SearchDev s, LeafBatc
     __shared__ uint32_t tnode[TZ_MAX_DEPTH];
     __shared__ uint32_t tvis[TZ_MAX_DEPTH];
     __shared__ uint8_t reach[NN * 4];
+    float* prow = nullptr;
+    if constexpr (RULE == TZ_SELECT_IMPROVED) {
+        __shared__ float row[SelectRow<N, RULE>::LEN];
+        prow = row;
+    }
     load_state(&root_env, &s.env[g]);
     const size_t base = slab_base(s, s.bank[g], g);
     const float beta = s.betas[g];
@@ -475,7 +592,7 @@ __global__ __launch_bounds__(64) void descend_batch_kernel(SearchDev s, LeafBatc
         __syncthreads();
         int depth = 0;
         Ev known{0, 0};
-        const int kind = forward_walk<N>(s, base, env, tnode, tvis, 0, beta, depth, known);
+        const int kind = forward_walk<N, RULE>(s, base, env, tnode, tvis, 0, beta, depth, known, prow);
         __syncthreads();
         forwards++;
         if (kind == 2) break;
@@ -1128,6 +1245,15 @@ __global__ __launch_bounds__(64) void gumbel_fixup_kernel(SearchDev s) {
         default: return tz_fail(TZ_EINVAL, "unsupported board size"); \
     }
 
+// the instantiation of the walk for SearchDev::select_rule; used inside TZ_DISPATCH_N
+#define TZ_DISPATCH_RULE(rule, CALL)                                              \
+    switch (rule) {                                                               \
+        case TZ_SELECT_PUCT: { constexpr int RB = TZ_SELECT_PUCT; CALL; } break;   \
+        case TZ_SELECT_UCT: { constexpr int RB = TZ_SELECT_UCT; CALL; } break;     \
+        case TZ_SELECT_IMPROVED: { constexpr int RB = TZ_SELECT_IMPROVED; CALL; } break; \
+        default: return tz_fail(TZ_EINVAL, "unknown selection rule");             \
+    }
+
 // diagnostic: the f32 primitives the tree kernels rely on being bit-identical with the host
 __global__ void device_math_kernel(int op, const float* a, const float* b, float* out, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1165,7 +1291,7 @@ extern "C" int tz_device_math(int op, const float* a, const float* b, float* out
 }
 
 int tz_tree_descend(const SearchDev& s, bool from_start_nodes, hipStream_t st) {
-    TZ_DISPATCH_N(s.n, (descend_kernel<NB><<<s.batch, 64, 0, st>>>(s, from_start_nodes ? 1 : 0)));
+    TZ_DISPATCH_N(s.n, TZ_DISPATCH_RULE(s.select_rule, (descend_kernel<NB, RB><<<s.batch, 64, 0, st>>>(s, from_start_nodes ? 1 : 0))));
     TZ_LAUNCH_CHECK();
     return TZ_OK;
 }
@@ -1247,7 +1373,7 @@ int tz_tree_principal_variation(const SearchDev& s, int game, uint16_t* moves_de
     return TZ_OK;
 }
 int tz_tree_descend_batch(const SearchDev& s, const LeafBatchDev& b, hipStream_t st) {
-    TZ_DISPATCH_N(s.n, (descend_batch_kernel<NB><<<s.batch, 64, 0, st>>>(s, b)));
+    TZ_DISPATCH_N(s.n, TZ_DISPATCH_RULE(s.select_rule, (descend_batch_kernel<NB, RB><<<s.batch, 64, 0, st>>>(s, b))));
     TZ_LAUNCH_CHECK();
     return TZ_OK;
 }
