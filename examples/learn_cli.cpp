@@ -6,6 +6,9 @@
 //
 //   g++ -std=c++17 -O2 examples/learn_cli.cpp -Iinclude -Ltakzero_amd -ltakzero_hip -Wl,-rpath,$PWD/takzero_amd -o learn_cli
 //   ./learn_cli --directory DIR --arch 5 --steps 100000
+// --train-rnd (net5): the steps of the main loop also train the RND predictor (loss_rnd, learn/src/main.rs:404-405) and min / max are
+// calibrated (update_rnd, :415-416) on reference positions made from --seed before every model file, and every
+// --rnd-calibrate-every steps when that is given.
 #include <dirent.h>
 
 #include <algorithm>
@@ -56,9 +59,18 @@ static int on_step(void* user, int64_t step, const float* losses, const tz_state
     return 0;
 }
 
+static const char* USAGE =
+    "usage: learn_cli --directory DIR [options]\n"
+    "  --arch 4|5|6|100  --n N  --blocks K  --batch B  --steps S  --seed X\n"
+    "  --pre-training-steps S  --initial-targets T  --steps-before-reanalyze S  --min-selfplay T  --min-reanalyze T\n"
+    "  --steps-per-save S  --steps-per-checkpoint S  --read-interval SEC  --sleep SEC  --wait-limit SEC  --verbose\n"
+    "  --train-rnd               net5 only: train the RND predictor in every step of the main loop and calibrate min / max\n"
+    "                            before every model file (reference positions from --seed)\n"
+    "  --rnd-calibrate-every N   also calibrate every N steps (default 0: only before model files)\n";
+
 int main(int argc, char** argv) {
     std::string directory;
-    int arch = TZ_ARCH_NET5, n = 5, blocks = 0, batch = 128, verbose = 0;
+    int arch = TZ_ARCH_NET5, n = 5, blocks = 0, batch = 128, verbose = 0, train_rnd = 0, rnd_calibrate_every = 0;
     long long steps = -1, pre_training_steps = 1000, initial_targets = 128 * 2000, steps_before_reanalyze = 5000;
     int min_selfplay = 10000, min_reanalyze = 2000, steps_per_save = 100, steps_per_checkpoint = 50000;
     double read_interval = 10.0, sleep_s = 30.0, wait_limit = -1.0;
@@ -84,13 +96,26 @@ int main(int argc, char** argv) {
         else if (a == "--sleep") sleep_s = atof(next());
         else if (a == "--wait-limit") wait_limit = atof(next());
         else if (a == "--verbose") verbose = 1;
-        else {
+        else if (a == "--train-rnd") train_rnd = 1;
+        else if (a == "--rnd-calibrate-every") rnd_calibrate_every = atoi(next());
+        else if (a == "--help" || a == "-h") {
+            fputs(USAGE, stdout);
+            return 0;
+        } else {
             fprintf(stderr, "unknown argument %s\n", a.c_str());
             return 2;
         }
     }
     if (directory.empty()) {
-        fprintf(stderr, "usage: learn_cli --directory DIR [--arch 4|5|6|100 --n N --blocks K --batch B --steps S --seed X ...]\n");
+        fputs(USAGE, stderr);
+        return 2;
+    }
+    if (train_rnd && arch != TZ_ARCH_NET5) {
+        fprintf(stderr, "--train-rnd needs --arch 5: only net5 has RND networks\n");
+        return 2;
+    }
+    if (rnd_calibrate_every < 0) {
+        fprintf(stderr, "--rnd-calibrate-every must not be negative\n");
         return 2;
     }
     if (arch == TZ_ARCH_NET5) n = 5;
@@ -161,10 +186,20 @@ int main(int argc, char** argv) {
             CHECK(tz_trainer_save(trainer, (directory + name).c_str()));
         }
     }
-    CHECK(tz_trainer_save(trainer, (directory + "/model_latest.ot").c_str()));
     tz_learn* loop = nullptr;
     CHECK(tz_learn_create(trainer, 4, seed, 4, 4, &loop));
     CHECK(tz_learn_set_save_points(loop, steps_per_save, steps_per_checkpoint, hash ? net : nullptr));
+    if (train_rnd) {
+        // reference_games (learn/src/rnd_normalization.rs:44-47): 256 positions at ply 4, 256 at ply 120
+        std::vector<tz_state> early(256), late(256);
+        tz_search* mcts = nullptr;
+        CHECK(tz_search_create(nullptr, TZ_AGENT_DUMMY, 256, n, 4, 1 << 10, &mcts));
+        CHECK(tz_learn_rnd_reference(mcts, seed, 256, 4, 256, 120, early.data(), late.data()));
+        tz_search_destroy(mcts);
+        CHECK(tz_learn_set_rnd(loop, 1, early.data(), 256, late.data(), 256, rnd_calibrate_every));
+        CHECK(tz_trainer_rnd_calibrate(trainer, early.data(), 256, late.data(), 256, 1, nullptr, nullptr));
+    }
+    CHECK(tz_trainer_save(trainer, (directory + "/model_latest.ot").c_str()));
     int64_t model_steps = starting_steps;
     const int rc = tz_learn_run(loop, directory.c_str(), starting_steps, steps, min_selfplay, min_reanalyze, steps_before_reanalyze, read_interval,
                                 sleep_s, wait_limit, on_step, &verbose, &model_steps);

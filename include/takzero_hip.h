@@ -451,6 +451,35 @@ int tz_trainer_get_extras(tz_trainer* t, void* out, uint64_t cap, uint64_t* byte
 int tz_trainer_from_net(tz_trainer* t, tz_net* net);
 int tz_trainer_to_net(tz_trainer* t, tz_net* net);
 
+/* ---------- Training net5's RND predictor in the step (net5.rs:193-218; learn/src/main.rs:404-405, 415-416) ----------
+ * The reference ships loss_rnd = forward_rnd(input, true).mean() and update_rnd switched off by comments; here both are present
+ * and off until asked for.  With it off a trainer does exactly what it did without these calls.
+ * tz_trainer_rnd_enable: on != 0 switches the distillation step on.  tz_trainer_step then also runs both RND MLPs on x / sum(x^2)
+ * of the batch's planes (net5.rs:126-127), takes loss_rnd = mean_b |learning - target|^2 (net5.rs:203, main.rs:404), its gradient
+ * through the predictor only (the target is detached, net5.rs:197-202) and, with apply_step, Adam on the six rnd_learning.*
+ * variables with a step count of their own (the feature may be switched on in the middle of a run; torch's Adam counts per
+ * parameter).  train_ube has no bearing on it; rnd_target.*, min and max never change in a step.  While enabled, the six
+ * rnd_learning.* names answer to tz_trainer_get_tensor / _set_tensor (what 0..3, weights as [out][in]); tz_trainer_tensor_count /
+ * _info list what they always list.  Save, to_net and get_extras carry the current predictor; a load re-uploads the model's.
+ * TZ_EINVAL unless the trainer is TZ_ARCH_NET5; TZ_ESTATE when the loaded variables hold no rnd_learning.* / rnd_target.* /
+ * min / max. */
+int tz_trainer_rnd_enable(tz_trainer* t, int on);
+/* loss_rnd (main.rs:404) and forward_rnd (net5.rs:193-204) [batch] of the last step, computed before that step's update.
+ * Either pointer may be NULL.  TZ_ESTATE before the first enabled step. */
+int tz_trainer_rnd_last(tz_trainer* t, float* loss_out, float* raw_out /*[batch]*/);
+/* What the last RND forward (a step's, or the last chunk of a calibration) left in an MLP (net5.rs:114-148): which 0 = learning,
+ * 1 = target; layer 0, 1 = after the ReLU of input_linear / hidden_linear, [batch][1024]; 2 = the output, [batch][512].
+ * out_cap in floats.  For tests, like tz_trainer_activation. */
+int tz_trainer_rnd_activation(tz_trainer* t, int which, int layer, float* out, uint64_t out_cap);
+/* update_rnd (learn/src/rnd_normalization.rs:74-78): min of forward_rnd over the early positions, max over the late ones (eval
+ * mode, which for these MLPs is the training graph; any counts >= 1, processed in chunks of the trainer's batch).  apply != 0 stores
+ * them in the variables min / max (update_rnd_normalization, net5.rs:213-218).  min_out / max_out may be NULL.
+ * If !(max > min) the call returns TZ_ESTATE and, with apply set, leaves the variables alone.  The reference has no such guard:
+ * it would store them, and normalized_rnd (net5.rs:206-211) would divide by zero.  TZ_ESTATE also while RND training is not
+ * enabled. */
+int tz_trainer_rnd_calibrate(tz_trainer* t, const tz_state* early, int n_early, const tz_state* late, int n_late, int apply,
+                             float* min_out, float* max_out);
+
 /* ---------- learn::main above the step (learn/src/main.rs:99-319, 486-516), native host code (csrc/tz_host_learn.cpp) ----------
  * The two target buffers with forced-use counts (SELFPLAY / REANALYZE_TARGET_FORCED_USES, :59-60) fed by tailing the
  * target files, create_batch (uniform sampling without replacement, a random board symmetry per target, dense
@@ -475,6 +504,22 @@ int tz_learn_run(tz_learn* l, const char* directory, int64_t starting_steps, int
  * the training loop; hash_net (may be NULL): a SimHash net whose set is updated with every batch (:418) and saved as
  * `bitvec.bin` beside the model.  0 = no such save point. */
 int tz_learn_set_save_points(tz_learn* l, int steps_per_save, int steps_per_checkpoint, tz_net* hash_net);
+/* RND training inside the loop (learn/src/main.rs:404-405, 415-416): train_rnd != 0 enables it on the loop's trainer
+ * (tz_trainer_rnd_enable; 0 disables it), so every step of tz_learn_step / tz_learn_run trains the predictor.  early / late (copied;
+ * may be NULL with a count of 0) are the reference positions of update_rnd: with them, tz_learn_run calibrates with apply = 1
+ * immediately before every model file it writes and before every on_step callback that falls on a multiple of calibrate_every
+ * (> 0), so that a saved model's min / max belong to its weights.  The commented-out reference calibrates after every step: two
+ * extra forwards of 256 positions for values that only a saved model hands on. */
+int tz_learn_set_rnd(tz_learn* l, int train_rnd, const tz_state* early, int n_early, const tz_state* late, int n_late,
+                     int calibrate_every);
+/* reference_games (learn/src/rnd_normalization.rs:23-58): game i of n_early plays early_ply + i % 2 uniformly random legal moves
+ * from the empty board, game i of n_late late_ply + i % 2 (the reference: 256 at ply 4, 256 at ply 120); the positions reached go
+ * to early_out[n_early] / late_out[n_late].  Played on `search` (any agent kind; its positions and trees are overwritten) with the
+ * calls of pre-training's random games.  Draws come from a counter-based generator keyed by (seed, game, ply): the reference's
+ * stream is unpinned.  A game that ends early contributes its last non-terminal position (the net never sees a terminal one; the
+ * reference keeps the terminal position, which is unpinned too). */
+int tz_learn_rnd_reference(tz_search* search, uint64_t seed, int n_early, int early_ply, int n_late, int late_ply,
+                           tz_state* early_out, tz_state* late_out);
 
 /* Diagnostic: evaluates on the device the f32 primitives the tree kernels must compute exactly as
  * the host does (op 0 exp, 1 ln, 2 sqrt, 3 a/b, 4 0.997^int(a), 5 (a+b)*a). */

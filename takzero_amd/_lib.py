@@ -43,6 +43,8 @@ SYMBOLS = [
     "tz_learn_create", "tz_learn_destroy", "tz_learn_feed", "tz_learn_add_lines", "tz_learn_buffer_len", "tz_learn_step", "tz_learn_run", "tz_learn_last_batch",
     "tz_search_simulate_batch", "tz_search_principal_variation", "tz_search_batch_profile",
     "tz_search_set_selection", "tz_search_get_selection",
+    "tz_trainer_rnd_enable", "tz_trainer_rnd_last", "tz_trainer_rnd_activation", "tz_trainer_rnd_calibrate", "tz_learn_set_rnd",
+    "tz_learn_rnd_reference",
 ]
 
 _lib = None
@@ -187,6 +189,12 @@ def load():
     lib.tz_trainer_step.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, vp]
     lib.tz_trainer_outputs.argtypes = [vp, vp, vp, vp]
     lib.tz_trainer_activation.argtypes = [vp, ci, vp, C.c_uint64]
+    lib.tz_trainer_rnd_enable.argtypes = [vp, ci]
+    lib.tz_trainer_rnd_last.argtypes = [vp, C.POINTER(cf), vp]
+    lib.tz_trainer_rnd_activation.argtypes = [vp, ci, ci, vp, C.c_uint64]
+    lib.tz_trainer_rnd_calibrate.argtypes = [vp, vp, ci, vp, ci, ci, C.POINTER(cf), C.POINTER(cf)]
+    lib.tz_learn_set_rnd.argtypes = [vp, ci, vp, ci, vp, ci, ci]
+    lib.tz_learn_rnd_reference.argtypes = [vp, C.c_uint64, ci, ci, ci, ci, vp, vp]
     _lib = lib
     return lib
 

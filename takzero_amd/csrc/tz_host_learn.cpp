@@ -4,6 +4,7 @@
 // with the preparation of the next batch, buffer_lengths.txt, and the save points (the model files themselves are
 // written by a callback: the LibTorch archive writer is a separate host tool).  takzero_amd/learn.py is the same loop in
 // Python.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -69,6 +70,10 @@ struct tz_learn {
     tz_net* hash_net = nullptr;           // SimHash nets: update_counts after every step (:418), bitvec.bin beside the model
     std::thread writer;                   // the archive of the previous save point, written behind the training loop
     std::string writer_error;
+    // RND training (tz_learn_set_rnd): the reference positions of update_rnd and how often the loop calibrates between save points
+    std::vector<tz_state> rnd_early, rnd_late;
+    int rnd_calibrate_every = 0;
+    bool train_rnd = false;
 };
 
 namespace {
@@ -197,6 +202,21 @@ int make_batch(tz_learn* l, bool using_reanalyze, bool augment, int slot) {
     return TZ_OK;
 }
 
+// update_rnd with apply (learn/src/main.rs:415-416), when RND training is on and the loop holds reference positions
+int rnd_calibrate(tz_learn* l) {
+    if (!l->train_rnd || l->rnd_early.empty() || l->rnd_late.empty()) return TZ_OK;
+    return tz_trainer_rnd_calibrate(l->trainer, l->rnd_early.data(), (int)l->rnd_early.size(), l->rnd_late.data(), (int)l->rnd_late.size(), 1,
+                                    nullptr, nullptr);
+}
+
+// the project's counter-based draws (as Net::new's initialisers): a 64-bit finaliser over the key
+uint64_t mix64(uint64_t x) {
+    x += 0x9e3779b97f4a7c15ull;
+    x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
+    x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
+    return x ^ (x >> 31);
+}
+
 int step_batch(tz_learn* l, int slot, int train_ube, float* losses) {
     auto& T = l->tensors[slot];
     return tz_trainer_step(l->trainer, T.states.data(), T.policy.data(), T.mask.data(), T.value.data(), T.ube.data(), train_ube, 1, losses);
@@ -316,6 +336,8 @@ int tz_learn_run(tz_learn* l, const char* directory, int64_t starting_steps, int
         const bool latest = l->steps_per_save > 0 && step_no % l->steps_per_save == 0;
         const bool numbered = l->steps_per_checkpoint > 0 && step_no % l->steps_per_checkpoint == 0;
         if (!latest && !numbered) return TZ_OK;
+        int rcal = rnd_calibrate(l);   // a saved model's min / max belong to its weights
+        if (rcal) return rcal;
         if (l->writer.joinable()) l->writer.join();
         if (!l->writer_error.empty()) return tz_fail(TZ_EINVAL, "tz_learn_run: writing a model file failed: " + l->writer_error);
         auto snap = std::make_shared<TensorStore>();
@@ -340,6 +362,7 @@ int tz_learn_run(tz_learn* l, const char* directory, int64_t starting_steps, int
             std::vector<uint32_t> idx(l->B);
             if ((r = tz_net_hash_indices(l->hash_net, l->B, l->tensors[pending_slot].states.data(), idx.data(), 1))) return r;
         }
+        if (l->rnd_calibrate_every > 0 && pending_step % l->rnd_calibrate_every == 0 && (r = rnd_calibrate(l))) return r;
         if ((r = save_point(pending_step))) return r;
         if (on_step && on_step(user, pending_step, pending_losses, l->tensors[pending_slot].states.data(), l->B))
             return tz_fail(TZ_ESTATE, "tz_learn_run: the on_step callback asked to stop");
@@ -396,6 +419,97 @@ int tz_learn_set_save_points(tz_learn* l, int steps_per_save, int steps_per_chec
     l->steps_per_save = steps_per_save;
     l->steps_per_checkpoint = steps_per_checkpoint;
     l->hash_net = hash_net;
+    return TZ_OK;
+}
+
+int tz_learn_set_rnd(tz_learn* l, int train_rnd, const tz_state* early, int n_early, const tz_state* late, int n_late,
+                     int calibrate_every) {
+    if (!l || n_early < 0 || n_late < 0 || (n_early > 0 && !early) || (n_late > 0 && !late) || calibrate_every < 0)
+        return tz_fail(TZ_EINVAL, "tz_learn_set_rnd: bad argument");
+    if (l->writer.joinable()) l->writer.join();
+    int rc = tz_trainer_rnd_enable(l->trainer, train_rnd ? 1 : 0);
+    if (rc) return rc;
+    l->train_rnd = train_rnd != 0;
+    l->rnd_early.assign(early, early + n_early);
+    l->rnd_late.assign(late, late + n_late);
+    l->rnd_calibrate_every = calibrate_every;
+    return TZ_OK;
+}
+
+// reference_games (learn/src/rnd_normalization.rs:23-58) on a search handle: the games of one set are played in waves of the handle's
+// batch with the calls of pre-training's random games (simulate once to expand the root, read its children, step, restart the
+// finished games).  A game that is done keeps receiving random moves until its wave is; they are not looked at.
+int tz_learn_rnd_reference(tz_search* search, uint64_t seed, int n_early, int early_ply, int n_late, int late_ply,
+                           tz_state* early_out, tz_state* late_out) {
+    if (!search || n_early < 0 || n_late < 0 || early_ply < 0 || late_ply < 0 || (n_early > 0 && !early_out) || (n_late > 0 && !late_out))
+        return tz_fail(TZ_EINVAL, "tz_learn_rnd_reference: bad argument");
+    int B = 0, n = 0, half_komi = 0, amax = 0;
+    int rc = tz_search_shape(search, &B, &n, &half_komi, &amax);
+    if (rc) return rc;
+    std::string tps;
+    for (int r = 0; r < n; r++) tps += (r ? "/x" : "x") + std::to_string(n);
+    tps += " 1 1";
+    tz_state empty;
+    if ((rc = tz_state_from_tps(tps.c_str(), n, half_komi, &empty))) return rc;
+    std::vector<int32_t> idx(B), zeros(B, 0);
+    for (int g = 0; g < B; g++) idx[g] = g;
+    std::vector<tz_state> start(B, empty), cur(B), prev(B);
+    std::vector<float> betas(B, 0.0f);
+    std::vector<tz_root_info> info(B);
+    std::vector<uint16_t> moves, actions(B);
+    std::vector<int8_t> term(B);
+    std::vector<int> played(B), target(B);
+    std::vector<char> done(B);
+    for (int set = 0; set < 2; set++) {
+        const int count = set ? n_late : n_early, ply = set ? late_ply : early_ply;
+        tz_state* out = set ? late_out : early_out;
+        for (int base = 0; base < count; base += B) {
+            const int wave = std::min(B, count - base);
+            if ((rc = tz_search_set_positions(search, B, idx.data(), start.data()))) return rc;
+            for (int g = 0; g < B; g++) {
+                played[g] = 0;
+                target[g] = ply + (base + g) % 2;
+                done[g] = g >= wave;
+            }
+            for (;;) {
+                if ((rc = tz_search_get_positions(search, cur.data()))) return rc;
+                bool all = true;
+                for (int g = 0; g < wave; g++) {
+                    if (!done[g] && played[g] == target[g]) {
+                        out[base + g] = cur[g];
+                        done[g] = 1;
+                    }
+                    all = all && done[g];
+                }
+                if (all) break;
+                if ((rc = tz_search_simulate(search, betas.data(), 1))) return rc;
+                if ((rc = tz_search_root_info(search, info.data()))) return rc;
+                int w = 1;
+                for (int g = 0; g < B; g++) w = std::max(w, (int)info[g].n_children);
+                moves.resize((size_t)B * w);
+                if ((rc = tz_search_root_children(search, w, moves.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))) return rc;
+                for (int g = 0; g < B; g++) {
+                    const int nc = (int)info[g].n_children;
+                    // key: (seed, game, ply); the two sets count their games apart
+                    const uint64_t game = ((uint64_t)set << 32) | (uint64_t)(base + g);
+                    const uint64_t u = mix64(mix64(mix64(seed) ^ game) ^ (uint64_t)played[g]);
+                    const int j = nc > 0 ? std::min(nc - 1, (int)((double)(u >> 11) * (1.0 / 9007199254740992.0) * nc)) : 0;
+                    actions[g] = nc > 0 ? moves[(size_t)g * w + j] : (uint16_t)0xFFFF;
+                }
+                prev = cur;
+                if ((rc = tz_search_step(search, actions.data()))) return rc;
+                if ((rc = tz_search_restart_terminal(search, zeros.data(), term.data()))) return rc;
+                for (int g = 0; g < wave; g++) {
+                    if (done[g]) continue;
+                    played[g]++;
+                    if (term[g] != TZ_TERMINAL_NONE) {   // the game ended early: its last non-terminal position
+                        out[base + g] = prev[g];
+                        done[g] = 1;
+                    }
+                }
+            }
+        }
+    }
     return TZ_OK;
 }
 

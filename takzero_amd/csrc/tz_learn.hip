@@ -10,6 +10,9 @@
 //   forward       c = im2col(x) x W;  BatchNorm with batch statistics;  ReLU (+ skip)
 //   backward      dW = im2col(x)^T x dc  (A-transposed GEMM);  dx = im2col(dc) x W'  with W' = taps mirrored, ci/co swapped
 //   parameters, gradients and the two Adam moments live in four parallel arenas; one Adam launch per step.
+//
+// Optional (tz_trainer_rnd_enable, off by default): net5's RND predictor is trained in the same step (net5.rs:193-218;
+// learn/src/main.rs:404-405) by a chain of small launches on a stream of its own, see "RND distillation" below.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -709,12 +712,13 @@ __global__ void losses_kernel(const float* lp, const float* lv, const float* lu,
 }
 
 // torch.optim.Adam (tch nn::Adam::default(): beta1 0.9, beta2 0.999, eps 1e-8, no weight decay, no amsgrad).
-// group[block of 1024 elements]: 0 = not trained, 1 = stepped every call, 2 = the UBE head (stepped when trained).
+// group[block of 1024 elements]: 0 = not trained, 1 = stepped every call, 2 = the UBE head (stepped when trained),
+// 3 = the RND predictor (its own arena and launch; counts its own steps, as torch's Adam does per parameter).
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ P, const float* __restrict__ G, float* __restrict__ M1,
                                                    float* __restrict__ M2, const uint8_t* __restrict__ group, float lr,
-                                                   int t_main, int t_ube) {
+                                                   int t_main, int t_ube, int t_rnd) {
     const int g = group[blockIdx.x];
-    const int step = g == 1 ? t_main : g == 2 ? t_ube : 0;
+    const int step = g == 1 ? t_main : g == 2 ? t_ube : g == 3 ? t_rnd : 0;
     if (step <= 0) return;
     const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
     const float bc1 = 1.f - powf(b1, (float)step), bc2 = 1.f - powf(b2, (float)step);
@@ -732,6 +736,117 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ P, const 
 }
 
 // ------------------------------------------------------------------------------------------------
+// RND distillation (net5.rs:114-148, 193-204; learn/src/main.rs:404): predictor and frozen target MLP 800 -> 1024 -> 1024 -> 512 on
+// x / sum(x^2), raw = |learning - target|^2 per position, loss_rnd = mean(raw), backward through the predictor only.  The linear
+// weights are kept like conv weights, [K = in (800 padded to 832)][N = out], so every contraction is gemm() above; what follows is
+// the rest of the chain.  Every sum has a fixed order.
+constexpr int RND_IN = 800, RND_INP = 832, RND_HID = 1024, RND_OUT = 512;
+
+// x / sum(x^2) of one board (one wave), written in the order of the reference's view of the NCHW planes: column = channel * 25 +
+// square (x0 is NHWC); columns 800 .. 831, the K padding, are zero.
+__global__ __launch_bounds__(64) void rnd_input_kernel(const float* __restrict__ x0, float* __restrict__ xr) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const float* x = x0 + (size_t)b * RND_IN;
+    float s = 0.f;
+    for (int i = lane; i < RND_IN; i += 64) s += x[i] * x[i];
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
+    s = __shfl(s, 0);
+    float* y = xr + (size_t)b * RND_INP;
+    for (int i = lane; i < RND_INP; i += 64) {
+        const int c = i / 25, sq = i - c * 25;
+        y[i] = i < RND_IN ? x[sq * 32 + c] / s : 0.f;
+    }
+}
+
+// h = relu(h) in place (the bias is added by the GEMM's epilogue)
+__global__ void rnd_relu_kernel(float* __restrict__ h, size_t total) {
+    const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i >= total) return;
+    float4 v = *(float4*)(h + i);
+    v.x = fmaxf(v.x, 0.f);
+    v.y = fmaxf(v.y, 0.f);
+    v.z = fmaxf(v.z, 0.f);
+    v.w = fmaxf(v.w, 0.f);
+    *(float4*)(h + i) = v;
+}
+
+// d = d * (h > 0) in place: ReLU's derivative is zero where the stored activation is zero, as in the trunk
+__global__ void rnd_relu_bwd_kernel(float* __restrict__ d, const float* __restrict__ h, size_t total) {
+    const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i >= total) return;
+    float4 v = *(float4*)(d + i);
+    const float4 a = *(const float4*)(h + i);
+    v.x = a.x > 0.f ? v.x : 0.f;
+    v.y = a.y > 0.f ? v.y : 0.f;
+    v.z = a.z > 0.f ? v.z : 0.f;
+    v.w = a.w > 0.f ? v.w : 0.f;
+    *(float4*)(d + i) = v;
+}
+
+// raw[b] = sum_j (learning[b][j] - target[b][j])^2 (net5.rs:203) and, when asked for, dY = 2 (learning - target) / batch.
+// One workgroup per position, two columns per thread, a fixed tree over the 256 partial sums.
+__global__ __launch_bounds__(256) void rnd_distance_kernel(const float* __restrict__ learning, const float* __restrict__ target,
+                                                           int batch, float* __restrict__ raw, float* __restrict__ dY) {
+    __shared__ float red[256];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const size_t i0 = (size_t)b * RND_OUT + t, i1 = i0 + 256;
+    const float d0 = learning[i0] - target[i0], d1 = learning[i1] - target[i1];
+    if (dY) {
+        dY[i0] = 2.f * d0 / (float)batch;
+        dY[i1] = 2.f * d1 / (float)batch;
+    }
+    red[t] = d0 * d0 + d1 * d1;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) red[t] += red[t + o];
+        __syncthreads();
+    }
+    if (t == 0) raw[b] = red[0];
+}
+
+// loss_rnd = mean over the batch, in position order
+__global__ void rnd_loss_kernel(const float* __restrict__ raw, int batch, float* __restrict__ out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double s = 0.0;
+    for (int b = 0; b < batch; b++) s += raw[b];
+    out[0] = (float)(s / batch);
+}
+
+// out[0] = min, out[1] = max of raw[0 .. count)
+__global__ __launch_bounds__(256) void rnd_minmax_kernel(const float* __restrict__ raw, int count, float* __restrict__ out) {
+    __shared__ float lo[256], hi[256];
+    const int t = threadIdx.x;
+    float a = INFINITY, b = -INFINITY;
+    for (int i = t; i < count; i += 256) {
+        a = fminf(a, raw[i]);
+        b = fmaxf(b, raw[i]);
+    }
+    lo[t] = a;
+    hi[t] = b;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) {
+            lo[t] = fminf(lo[t], lo[t + o]);
+            hi[t] = fmaxf(hi[t], hi[t + o]);
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        out[0] = lo[0];
+        out[1] = hi[0];
+    }
+}
+
+// out[C][R] = in[R][C]^T, R and C multiples of 32: the weight matrix of a linear layer's data gradient
+__global__ __launch_bounds__(256) void rnd_transpose_kernel(const float* __restrict__ in, float* __restrict__ out, int R, int C) {
+    __shared__ float tile[32][33];
+    const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    for (int i = ty; i < 32; i += 8) tile[i][tx] = in[(size_t)(r0 + i) * C + c0 + tx];
+    __syncthreads();
+    for (int i = ty; i < 32; i += 8) out[(size_t)(c0 + i) * R + r0 + tx] = tile[tx][i];
+}
+
+// ------------------------------------------------------------------------------------------------
 struct Param {
     std::string name;
     size_t off = 0, slots = 0;     // offset / extent in the arenas (multiple of 1024)
@@ -739,6 +854,33 @@ struct Param {
     int co = 0, ci = 0, ld = 0, kp = 0;
     size_t count = 0;              // elements in the reference's tensor
     int group = 0;
+};
+
+// The RND side of a net5 trainer, allocated when tz_trainer_rnd_enable first switches it on.  The six tensors of one MLP lie in one
+// arena at off[]: input_linear.weight [832][1024], .bias, hidden_linear.weight [1024][1024], .bias, final_linear.weight [1024][512],
+// .bias.  The predictor has the four arenas of the trunk (parameters, gradients, two moments), the target its parameters only.
+struct RndLayer {
+    const char* name;
+    int in, inp, out;
+};
+const RndLayer RND_LAYERS[3] = {{"input_linear", RND_IN, RND_INP, RND_HID}, {"hidden_linear", RND_HID, RND_HID, RND_HID},
+                                {"final_linear", RND_HID, RND_HID, RND_OUT}};
+struct Rnd {
+    bool allocated = false, on = false;
+    int t_rnd = 0;
+    size_t off[6] = {0, 0, 0, 0, 0, 0}, slots[6] = {0, 0, 0, 0, 0, 0}, total = 0;
+    float *P = nullptr, *G = nullptr, *M1 = nullptr, *M2 = nullptr, *T = nullptr;
+    uint8_t* group = nullptr;
+    float* xr = nullptr;                                   // [batch][832]
+    float* h[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // [learning, target][layer]: [batch][1024] after ReLU
+    float* out[2] = {nullptr, nullptr};                    // [batch][512]
+    float *dY = nullptr, *dH2 = nullptr, *dH1 = nullptr;   // gradients at the three layers' outputs
+    float *w2t = nullptr, *w3t = nullptr;                  // hidden / final weights transposed, for the data gradients
+    float *raw = nullptr, *loss = nullptr, *raw_cal = nullptr, *minmax = nullptr, *ws = nullptr;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_x0 = nullptr, ev_done = nullptr;
+    float last_loss = 0.f;
+    bool have_last = false;
 };
 
 }  // namespace
@@ -779,7 +921,10 @@ struct tz_trainer {
     int sk_groups = 512;
     float* sk_ws[2] = {nullptr, nullptr};
     std::vector<void*> allocs;
-    TensorStore extra;   // variables of the VarStore the step never touches (RND nets, SimHash matrix): carried through save / load
+    // variables of the VarStore the trunk's step never touches (RND nets, SimHash matrix): carried through save / load.  While RND
+    // training is enabled the device holds the current rnd_learning.*; rnd_download brings them here before anything reads them.
+    TensorStore extra;
+    Rnd rnd;
 };
 
 namespace {
@@ -850,7 +995,7 @@ int gemm(tz_trainer* t, bool at, const float* A, const float* B, float* C, const
         const int tiles_m = M / 64, tiles = tiles_m * (N / 64), S = K / 32;
         const long long total = (long long)tiles * S;
         const int G = (int)std::min<long long>(total, t->sk_groups);
-        float* ws = st == t->stream2 ? t->sk_ws[1] : t->sk_ws[0];
+        float* ws = st == t->stream2 ? t->sk_ws[1] : (t->rnd.stream && st == t->rnd.stream) ? t->rnd.ws : t->sk_ws[0];
         const int gn = gather_c ? t->n : 0;
         if (gather_c && at)
             gemm_sk_kernel<true, true><<<G, 256, 0, st>>>(A, B, C, bias, K, lda, ldb, ldc, acc, gn, gather_c, tiles_m, total, ws);
@@ -883,6 +1028,7 @@ int forward(tz_trainer* t) {
     const int M = t->M;
     const size_t act = (size_t)M * FILTERS;
     if ((rc = tz_nn_encode_planes(t->n, t->cin, t->states, t->batch, t->x0, t->stream))) return rc;
+    if (t->rnd.on) TZ_HIP(hipEventRecord(t->rnd.ev_x0, t->stream));   // the RND chain starts from the planes, beside the trunk
     for (int l = 0; l < t->layers; l++) {
         const float* in = l == 0 ? t->x0 : t->a[l - 1];
         const int C = l == 0 ? t->cin : FILTERS, Kp = l == 0 ? t->kp_in : 9 * FILTERS;
@@ -1028,6 +1174,179 @@ int backward(tz_trainer* t, int train_ube) {
     return TZ_OK;
 }
 
+// ---- RND chain ----
+const float* rnd_bias(const Rnd& r, const float* arena, int layer) { return arena + r.off[2 * layer + 1]; }
+
+// both MLPs on the planes in t->x0 (batch boards): xr, h[net][0], h[net][1], out[net]
+int rnd_forward(tz_trainer* t, hipStream_t st) {
+    Rnd& r = t->rnd;
+    const int B = t->batch;
+    int rc;
+    rnd_input_kernel<<<B, 64, 0, st>>>(t->x0, r.xr);
+    if ((rc = launch_check("rnd input"))) return rc;
+    const size_t hid = (size_t)B * RND_HID;
+    for (int net = 0; net < 2; net++) {
+        const float* W = net == 0 ? r.P : r.T;
+        if ((rc = gemm(t, false, r.xr, W + r.off[0], r.h[net][0], rnd_bias(r, W, 0), B, RND_HID, RND_INP, RND_INP, RND_HID, RND_HID, false, st)))
+            return rc;
+        rnd_relu_kernel<<<(unsigned)((hid / 4 + 255) / 256), 256, 0, st>>>(r.h[net][0], hid);
+        if ((rc = gemm(t, false, r.h[net][0], W + r.off[2], r.h[net][1], rnd_bias(r, W, 1), B, RND_HID, RND_HID, RND_HID, RND_HID, RND_HID, false, st)))
+            return rc;
+        rnd_relu_kernel<<<(unsigned)((hid / 4 + 255) / 256), 256, 0, st>>>(r.h[net][1], hid);
+        if ((rc = gemm(t, false, r.h[net][1], W + r.off[4], r.out[net], rnd_bias(r, W, 2), B, RND_OUT, RND_HID, RND_HID, RND_OUT, RND_OUT, false, st)))
+            return rc;
+    }
+    return launch_check("rnd forward");
+}
+
+// The whole distillation step on the RND stream: it waits for the planes only, so it runs beside the trunk's forward; the main stream
+// joins it (ev_done) before its own Adam launch.
+int rnd_chain(tz_trainer* t, int apply_step) {
+    Rnd& r = t->rnd;
+    const int B = t->batch;
+    hipStream_t st = r.stream;
+    int rc;
+    // the transposed weights of the two data gradients depend on the weights only: ahead of the wait for the planes
+    rnd_transpose_kernel<<<dim3(RND_OUT / 32, RND_HID / 32), 256, 0, st>>>(r.P + r.off[4], r.w3t, RND_HID, RND_OUT);
+    rnd_transpose_kernel<<<dim3(RND_HID / 32, RND_HID / 32), 256, 0, st>>>(r.P + r.off[2], r.w2t, RND_HID, RND_HID);
+    if ((rc = launch_check("rnd transpose"))) return rc;
+    TZ_HIP(hipStreamWaitEvent(st, r.ev_x0, 0));
+    if ((rc = rnd_forward(t, st))) return rc;
+    rnd_distance_kernel<<<B, 256, 0, st>>>(r.out[0], r.out[1], B, r.raw, r.dY);
+    rnd_loss_kernel<<<1, 1, 0, st>>>(r.raw, B, r.loss);
+    if ((rc = launch_check("rnd loss"))) return rc;
+    const size_t hid = (size_t)B * RND_HID;
+    const unsigned hid_blocks = (unsigned)((hid / 4 + 255) / 256);
+    // final layer: dW = h2^T x dY, db = column sums of dY, dH2 = dY x W^T masked by h2 > 0
+    if ((rc = gemm(t, true, r.h[0][1], r.dY, r.G + r.off[4], nullptr, RND_HID, RND_OUT, B, RND_HID, RND_OUT, RND_OUT, false, st))) return rc;
+    column_sum_kernel<<<RND_OUT / 32, 256, 0, st>>>(r.dY, B, RND_OUT, RND_OUT, r.G + r.off[5]);
+    if ((rc = gemm(t, false, r.dY, r.w3t, r.dH2, nullptr, B, RND_HID, RND_OUT, RND_OUT, RND_HID, RND_HID, false, st))) return rc;
+    rnd_relu_bwd_kernel<<<hid_blocks, 256, 0, st>>>(r.dH2, r.h[0][1], hid);
+    // hidden layer
+    if ((rc = gemm(t, true, r.h[0][0], r.dH2, r.G + r.off[2], nullptr, RND_HID, RND_HID, B, RND_HID, RND_HID, RND_HID, false, st))) return rc;
+    column_sum_kernel<<<RND_HID / 32, 256, 0, st>>>(r.dH2, B, RND_HID, RND_HID, r.G + r.off[3]);
+    if ((rc = gemm(t, false, r.dH2, r.w2t, r.dH1, nullptr, B, RND_HID, RND_HID, RND_HID, RND_HID, RND_HID, false, st))) return rc;
+    rnd_relu_bwd_kernel<<<hid_blocks, 256, 0, st>>>(r.dH1, r.h[0][0], hid);
+    // input layer: the gradient comes out in the weights' own layout [832][1024]; its padding rows are xr's zero columns times dH1
+    if ((rc = gemm(t, true, r.xr, r.dH1, r.G + r.off[0], nullptr, RND_INP, RND_HID, B, RND_INP, RND_HID, RND_HID, false, st))) return rc;
+    column_sum_kernel<<<RND_HID / 32, 256, 0, st>>>(r.dH1, B, RND_HID, RND_HID, r.G + r.off[1]);
+    if ((rc = launch_check("rnd backward"))) return rc;
+    if (apply_step) {
+        r.t_rnd++;
+        adam_kernel<<<(unsigned)(r.total / 1024), 256, 0, st>>>(r.P, r.G, r.M1, r.M2, r.group, t->lr, 0, 0, r.t_rnd);
+        if ((rc = launch_check("rnd adam"))) return rc;
+    }
+    TZ_HIP(hipEventRecord(r.ev_done, st));
+    return TZ_OK;
+}
+
+// index 0 .. 5 of an rnd_learning.* variable in the arena, -1 for any other name
+int rnd_index(const std::string& name, const char* net = "rnd_learning") {
+    for (int l = 0; l < 3; l++)
+        for (int part = 0; part < 2; part++)
+            if (name == std::string(net) + "." + RND_LAYERS[l].name + (part ? ".bias" : ".weight")) return 2 * l + part;
+    return -1;
+}
+std::string rnd_name(const char* net, int i) { return std::string(net) + "." + RND_LAYERS[i / 2].name + (i % 2 ? ".bias" : ".weight"); }
+size_t rnd_count(int i) { return i % 2 ? (size_t)RND_LAYERS[i / 2].out : (size_t)RND_LAYERS[i / 2].out * RND_LAYERS[i / 2].in; }
+
+// reference layout ([out][in] weights, biases as they are) <-> the arena's ([in, padded][out], padding zero)
+void rnd_pack(int i, const float* data, std::vector<float>& host, size_t slots) {
+    const RndLayer& L = RND_LAYERS[i / 2];
+    host.assign(slots, 0.f);
+    if (i % 2) {
+        memcpy(host.data(), data, sizeof(float) * L.out);
+        return;
+    }
+    for (int o = 0; o < L.out; o++)
+        for (int k = 0; k < L.in; k++) host[(size_t)k * L.out + o] = data[(size_t)o * L.in + k];
+}
+void rnd_unpack(int i, const std::vector<float>& host, float* out) {
+    const RndLayer& L = RND_LAYERS[i / 2];
+    if (i % 2) {
+        memcpy(out, host.data(), sizeof(float) * L.out);
+        return;
+    }
+    for (int o = 0; o < L.out; o++)
+        for (int k = 0; k < L.in; k++) out[(size_t)o * L.in + k] = host[(size_t)k * L.out + o];
+}
+
+bool rnd_variables_present(const tz_trainer* t) {
+    for (const char* net : {"rnd_learning", "rnd_target"})
+        for (int i = 0; i < 6; i++) {
+            auto it = t->extra.find(rnd_name(net, i));
+            if (it == t->extra.end() || it->second.data.size() != rnd_count(i)) return false;
+        }
+    for (const char* v : {"min", "max"}) {
+        auto it = t->extra.find(v);
+        if (it == t->extra.end() || it->second.data.size() != 1) return false;
+    }
+    return true;
+}
+
+// the carried rnd_learning.* / rnd_target.* go to the device (parameters only: gradients and moments stay)
+int rnd_upload(tz_trainer* t) {
+    Rnd& r = t->rnd;
+    std::vector<float> host;
+    TZ_HIP(hipStreamSynchronize(t->stream));
+    TZ_HIP(hipStreamSynchronize(r.stream));
+    for (int net = 0; net < 2; net++)
+        for (int i = 0; i < 6; i++) {
+            rnd_pack(i, t->extra.at(rnd_name(net ? "rnd_target" : "rnd_learning", i)).data.data(), host, r.slots[i]);
+            TZ_HIP(hipMemcpy((net ? r.T : r.P) + r.off[i], host.data(), r.slots[i] * sizeof(float), hipMemcpyHostToDevice));
+        }
+    return TZ_OK;
+}
+
+// ... and the current predictor comes back into the carried variables
+int rnd_download(tz_trainer* t) {
+    Rnd& r = t->rnd;
+    TZ_HIP(hipSetDevice(t->device));
+    TZ_HIP(hipStreamSynchronize(t->stream));
+    TZ_HIP(hipStreamSynchronize(r.stream));
+    std::vector<float> host;
+    for (int i = 0; i < 6; i++) {
+        host.resize(r.slots[i]);
+        TZ_HIP(hipMemcpy(host.data(), r.P + r.off[i], r.slots[i] * sizeof(float), hipMemcpyDeviceToHost));
+        HostTensor& h = t->extra[rnd_name("rnd_learning", i)];
+        h.data.resize(rnd_count(i));
+        rnd_unpack(i, host, h.data.data());
+    }
+    return TZ_OK;
+}
+
+int rnd_allocate(tz_trainer* t) {
+    Rnd& r = t->rnd;
+    if (r.allocated) return TZ_OK;
+    r.total = 0;
+    for (int i = 0; i < 6; i++) {
+        const RndLayer& L = RND_LAYERS[i / 2];
+        const size_t elems = i % 2 ? (size_t)L.out : (size_t)L.inp * L.out;
+        r.slots[i] = (elems + 1023) / 1024 * 1024;
+        r.off[i] = r.total;
+        r.total += r.slots[i];
+    }
+    const size_t B = (size_t)t->batch;
+    int rc;
+    if ((rc = dalloc(t, &r.P, r.total)) || (rc = dalloc(t, &r.G, r.total)) || (rc = dalloc(t, &r.M1, r.total)) ||
+        (rc = dalloc(t, &r.M2, r.total)) || (rc = dalloc(t, &r.T, r.total)) || (rc = dalloc(t, &r.group, r.total / 1024)) ||
+        (rc = dalloc(t, &r.xr, B * RND_INP)) || (rc = dalloc(t, &r.out[0], B * RND_OUT)) || (rc = dalloc(t, &r.out[1], B * RND_OUT)) ||
+        (rc = dalloc(t, &r.dY, B * RND_OUT)) || (rc = dalloc(t, &r.dH2, B * RND_HID)) || (rc = dalloc(t, &r.dH1, B * RND_HID)) ||
+        (rc = dalloc(t, &r.w2t, (size_t)RND_HID * RND_HID)) || (rc = dalloc(t, &r.w3t, (size_t)RND_HID * RND_OUT)) ||
+        (rc = dalloc(t, &r.raw, B)) || (rc = dalloc(t, &r.raw_cal, B)) || (rc = dalloc(t, &r.loss, (size_t)4)) ||
+        (rc = dalloc(t, &r.minmax, (size_t)4)) || (rc = dalloc(t, &r.ws, (size_t)t->sk_groups * 2 * 4096)))
+        return rc;
+    for (int net = 0; net < 2; net++)
+        for (int l = 0; l < 2; l++)
+            if ((rc = dalloc(t, &r.h[net][l], B * RND_HID))) return rc;
+    TZ_HIP(hipMemset(r.group, 3, r.total / 1024));
+    if (!r.stream) TZ_HIP(hipStreamCreate(&r.stream));
+    if (!r.ev_x0) TZ_HIP(hipEventCreateWithFlags(&r.ev_x0, hipEventDisableTiming));
+    if (!r.ev_done) TZ_HIP(hipEventCreateWithFlags(&r.ev_done, hipEventDisableTiming));
+    r.allocated = true;
+    return TZ_OK;
+}
+
 }  // namespace
 // ------------------------------------------------------------------------------------------------
 // C ABI (include/takzero_hip.h, "Trainer")
@@ -1167,6 +1486,12 @@ int tz_trainer_destroy(tz_trainer* t) {
     (void)hipSetDevice(t->device);
     (void)hipStreamSynchronize(t->stream);
     (void)hipStreamSynchronize(t->stream2);
+    if (t->rnd.stream) {
+        (void)hipStreamSynchronize(t->rnd.stream);
+        (void)hipStreamDestroy(t->rnd.stream);
+    }
+    if (t->rnd.ev_x0) (void)hipEventDestroy(t->rnd.ev_x0);
+    if (t->rnd.ev_done) (void)hipEventDestroy(t->rnd.ev_done);
     for (void* q : t->allocs) (void)hipFree(q);
     (void)hipStreamDestroy(t->stream);
     (void)hipStreamDestroy(t->stream2);
@@ -1207,6 +1532,20 @@ static float* arena_of(tz_trainer* t, int what) {
 // what: 0 parameter, 1 gradient of the last step, 2 / 3 Adam first / second moment.  Data in the reference's layout.
 int tz_trainer_set_tensor(tz_trainer* t, const char* name, int what, const float* data, uint64_t count) {
     if (!t || !name || !data) return tz_fail(TZ_EINVAL, "tz_trainer_set_tensor: null argument");
+    if (t->rnd.on && rnd_index(name) >= 0) {   // the predictor's variables answer while its training is enabled
+        Rnd& r = t->rnd;
+        const int i = rnd_index(name);
+        float* ra = what == 0 ? r.P : what == 1 ? r.G : what == 2 ? r.M1 : what == 3 ? r.M2 : nullptr;
+        if (!ra) return tz_fail(TZ_EINVAL, std::string("tz_trainer_set_tensor: unknown tensor ") + name);
+        if (count != rnd_count(i)) return tz_fail(TZ_EPARSE, std::string("tz_trainer_set_tensor: wrong size for ") + name);
+        TZ_HIP(hipSetDevice(t->device));
+        std::vector<float> host;
+        rnd_pack(i, data, host, r.slots[i]);
+        TZ_HIP(hipStreamSynchronize(t->stream));
+        TZ_HIP(hipStreamSynchronize(r.stream));
+        TZ_HIP(hipMemcpy(ra + r.off[i], host.data(), r.slots[i] * sizeof(float), hipMemcpyHostToDevice));
+        return TZ_OK;
+    }
     auto it = t->index.find(name);
     float* arena = arena_of(t, what);
     if (it == t->index.end() || !arena) return tz_fail(TZ_EINVAL, std::string("tz_trainer_set_tensor: unknown tensor ") + name);
@@ -1229,6 +1568,20 @@ int tz_trainer_set_tensor(tz_trainer* t, const char* name, int what, const float
 
 int tz_trainer_get_tensor(tz_trainer* t, const char* name, int what, float* out, uint64_t count) {
     if (!t || !name || !out) return tz_fail(TZ_EINVAL, "tz_trainer_get_tensor: null argument");
+    if (t->rnd.on && rnd_index(name) >= 0) {
+        Rnd& r = t->rnd;
+        const int i = rnd_index(name);
+        const float* ra = what == 0 ? r.P : what == 1 ? r.G : what == 2 ? r.M1 : what == 3 ? r.M2 : nullptr;
+        if (!ra) return tz_fail(TZ_EINVAL, std::string("tz_trainer_get_tensor: unknown tensor ") + name);
+        if (count != rnd_count(i)) return tz_fail(TZ_EPARSE, std::string("tz_trainer_get_tensor: wrong size for ") + name);
+        TZ_HIP(hipSetDevice(t->device));
+        std::vector<float> host(r.slots[i]);
+        TZ_HIP(hipStreamSynchronize(t->stream));
+        TZ_HIP(hipStreamSynchronize(r.stream));
+        TZ_HIP(hipMemcpy(host.data(), ra + r.off[i], r.slots[i] * sizeof(float), hipMemcpyDeviceToHost));
+        rnd_unpack(i, host, out);
+        return TZ_OK;
+    }
     auto it = t->index.find(name);
     float* arena = arena_of(t, what);
     if (it == t->index.end() || !arena) return tz_fail(TZ_EINVAL, std::string("tz_trainer_get_tensor: unknown tensor ") + name);
@@ -1260,6 +1613,10 @@ static std::vector<uint32_t> param_dims(const tz_trainer* t, const Param& p) {
 
 // The trainer's VarStore as a host store (current parameters and buffers + the carried extras)
 int tz_trainer_snapshot(tz_trainer* t, TensorStore& out) {
+    if (t->rnd.on) {
+        int rc = rnd_download(t);
+        if (rc) return rc;
+    }
     out = t->extra;
     for (const Param& p : t->params) {
         HostTensor h;
@@ -1285,6 +1642,13 @@ static int trainer_apply_store(tz_trainer* t, const TensorStore& st) {
     t->extra.clear();
     for (auto& kv : st)
         if (!t->index.count(kv.first)) t->extra[kv.first] = kv.second;
+    if (t->rnd.on) {   // the loaded model's RND nets replace the device's (moments stay, as for the other parameters)
+        if (!rnd_variables_present(t)) {
+            t->rnd.on = false;
+            return tz_fail(TZ_ESTATE, "trainer: the loaded model holds no RND variables; RND training is switched off");
+        }
+        return rnd_upload(t);
+    }
     return TZ_OK;
 }
 
@@ -1309,6 +1673,10 @@ int tz_trainer_load_weights_mem(tz_trainer* t, const void* data, size_t bytes) {
 // the carried variables alone as a .tzw container: out = NULL (or cap too small) asks for the size only
 int tz_trainer_get_extras(tz_trainer* t, void* out, uint64_t cap, uint64_t* bytes_out) {
     if (!t) return tz_fail(TZ_EINVAL, "tz_trainer_get_extras: null handle");
+    if (t->rnd.on) {
+        int rc = rnd_download(t);
+        if (rc) return rc;
+    }
     std::vector<unsigned char> blob;
     tzw_dump(t->extra, blob);
     if (bytes_out) *bytes_out = blob.size();
@@ -1361,20 +1729,28 @@ int tz_trainer_step(tz_trainer* t, const tz_state* states, const float* target_p
     // graph's two branches do not overlap the way the two streams do)
     if ((rc = mirror_all(t))) return rc;
     if ((rc = forward(t))) return rc;
+    if (t->rnd.on && (rc = rnd_chain(t, apply_step))) return rc;
     if ((rc = backward(t, train_ube))) return rc;
+    if (t->rnd.on) TZ_HIP(hipStreamWaitEvent(t->stream, t->rnd.ev_done, 0));
     if (apply_step) {
         t->t_main++;
         if (train_ube) t->t_ube++;
         adam_kernel<<<(unsigned)(t->total / 1024), 256, 0, t->stream>>>(t->P, t->G, t->M1, t->M2, t->group_dev, t->lr,
-                                                                        t->t_main, train_ube ? t->t_ube : 0);
+                                                                        t->t_main, train_ube ? t->t_ube : 0, 0);
         if ((rc = launch_check("adam"))) return rc;
     }
     float losses[4] = {0, 0, 0, 0};
     TZ_HIP(hipMemcpyAsync(losses, t->losses, sizeof(float) * 3, hipMemcpyDeviceToHost, t->stream));
+    if (t->rnd.on) TZ_HIP(hipMemcpyAsync(&losses[3], t->rnd.loss, sizeof(float), hipMemcpyDeviceToHost, t->stream));
     TZ_HIP(hipStreamSynchronize(t->stream));
+    if (t->rnd.on) {
+        t->rnd.last_loss = losses[3];
+        t->rnd.have_last = true;
+    }
     if (losses_out) memcpy(losses_out, losses, sizeof(float) * 3);
     if (!(losses[0] == losses[0]) || !(losses[1] == losses[1]) || !(losses[2] == losses[2]))
         return tz_fail(TZ_ENUMERIC, "tz_trainer_step: a loss is NaN");
+    if (t->rnd.on && !(losses[3] == losses[3])) return tz_fail(TZ_ENUMERIC, "tz_trainer_step: loss_rnd is NaN");
     return TZ_OK;
 }
 
@@ -1405,6 +1781,89 @@ int tz_trainer_activation(tz_trainer* t, int layer, float* out, uint64_t cap) {
     TZ_HIP(hipSetDevice(t->device));
     TZ_HIP(hipStreamSynchronize(t->stream));
     TZ_HIP(hipMemcpy(out, t->a[layer], real * sizeof(float), hipMemcpyDeviceToHost));
+    return TZ_OK;
+}
+
+// ---- RND training (net5.rs:193-218; learn/src/main.rs:404-405, 415-416; learn/src/rnd_normalization.rs:74-78) ----
+int tz_trainer_rnd_enable(tz_trainer* t, int on) {
+    if (!t) return tz_fail(TZ_EINVAL, "tz_trainer_rnd_enable: null handle");
+    if (t->arch != TZ_ARCH_NET5) return tz_fail(TZ_EINVAL, "tz_trainer_rnd_enable: only net5 has RND networks");
+    TZ_HIP(hipSetDevice(t->device));
+    int rc;
+    if (!on) {
+        if (t->rnd.on && (rc = rnd_download(t))) return rc;   // the trained predictor stays with the carried variables
+        t->rnd.on = false;
+        return TZ_OK;
+    }
+    if (t->rnd.on) return TZ_OK;
+    if (!rnd_variables_present(t))
+        return tz_fail(TZ_ESTATE, "tz_trainer_rnd_enable: the loaded variables hold no rnd_learning.* / rnd_target.* / min / max");
+    if ((rc = rnd_allocate(t))) return rc;
+    if ((rc = rnd_upload(t))) return rc;
+    t->rnd.on = true;
+    return TZ_OK;
+}
+
+int tz_trainer_rnd_last(tz_trainer* t, float* loss_out, float* raw_out) {
+    if (!t) return tz_fail(TZ_EINVAL, "tz_trainer_rnd_last: null handle");
+    if (!t->rnd.allocated || !t->rnd.have_last) return tz_fail(TZ_ESTATE, "tz_trainer_rnd_last: no step with RND training yet");
+    TZ_HIP(hipSetDevice(t->device));
+    TZ_HIP(hipStreamSynchronize(t->stream));
+    if (loss_out) *loss_out = t->rnd.last_loss;
+    if (raw_out) TZ_HIP(hipMemcpy(raw_out, t->rnd.raw, sizeof(float) * t->batch, hipMemcpyDeviceToHost));
+    return TZ_OK;
+}
+
+int tz_trainer_rnd_activation(tz_trainer* t, int which, int layer, float* out, uint64_t out_cap) {
+    if (!t || !out) return tz_fail(TZ_EINVAL, "tz_trainer_rnd_activation: null argument");
+    if (which < 0 || which > 1 || layer < 0 || layer > 2) return tz_fail(TZ_EINVAL, "tz_trainer_rnd_activation: no such network or layer");
+    if (!t->rnd.allocated) return tz_fail(TZ_ESTATE, "tz_trainer_rnd_activation: RND training was never enabled");
+    const size_t real = (size_t)t->batch * (layer == 2 ? RND_OUT : RND_HID);
+    if (out_cap < real) return tz_fail(TZ_EINVAL, "tz_trainer_rnd_activation: the buffer is too small");
+    TZ_HIP(hipSetDevice(t->device));
+    TZ_HIP(hipStreamSynchronize(t->stream));
+    TZ_HIP(hipStreamSynchronize(t->rnd.stream));
+    TZ_HIP(hipMemcpy(out, layer == 2 ? t->rnd.out[which] : t->rnd.h[which][layer], real * sizeof(float), hipMemcpyDeviceToHost));
+    return TZ_OK;
+}
+
+int tz_trainer_rnd_calibrate(tz_trainer* t, const tz_state* early, int n_early, const tz_state* late, int n_late, int apply,
+                             float* min_out, float* max_out) {
+    if (!t || !early || !late || n_early < 1 || n_late < 1) return tz_fail(TZ_EINVAL, "tz_trainer_rnd_calibrate: bad argument");
+    if (!t->rnd.on) return tz_fail(TZ_ESTATE, "tz_trainer_rnd_calibrate: RND training is not enabled");
+    Rnd& r = t->rnd;
+    TZ_HIP(hipSetDevice(t->device));
+    TZ_HIP(hipStreamSynchronize(t->stream));
+    const int B = t->batch;
+    std::vector<tz_state> chunk(B);
+    float found[2] = {INFINITY, -INFINITY};   // min over early, max over late
+    for (int set = 0; set < 2; set++) {
+        const tz_state* states = set ? late : early;
+        const int count = set ? n_late : n_early;
+        for (int c = 0; c < count; c += B) {
+            const int cnt = std::min(B, count - c);
+            for (int i = 0; i < B; i++) chunk[i] = states[c + (i < cnt ? i : 0)];   // the rows past cnt repeat one and are not read back
+            TZ_HIP(hipMemcpyAsync(t->states, chunk.data(), sizeof(tz_state) * B, hipMemcpyHostToDevice, r.stream));
+            int rc;
+            if ((rc = tz_nn_encode_planes(t->n, t->cin, t->states, B, t->x0, r.stream))) return rc;
+            if ((rc = rnd_forward(t, r.stream))) return rc;
+            rnd_distance_kernel<<<B, 256, 0, r.stream>>>(r.out[0], r.out[1], B, r.raw_cal, nullptr);
+            rnd_minmax_kernel<<<1, 256, 0, r.stream>>>(r.raw_cal, cnt, r.minmax);
+            if ((rc = launch_check("rnd calibrate"))) return rc;
+            float mm[2];
+            TZ_HIP(hipMemcpyAsync(mm, r.minmax, sizeof mm, hipMemcpyDeviceToHost, r.stream));
+            TZ_HIP(hipStreamSynchronize(r.stream));
+            if (set == 0) found[0] = fminf(found[0], mm[0]);
+            else found[1] = fmaxf(found[1], mm[1]);
+        }
+    }
+    if (min_out) *min_out = found[0];
+    if (max_out) *max_out = found[1];
+    if (!(found[1] > found[0])) return tz_fail(TZ_ESTATE, "tz_trainer_rnd_calibrate: max is not above min; the variables are left alone");
+    if (apply) {
+        t->extra["min"].data[0] = found[0];
+        t->extra["max"].data[0] = found[1];
+    }
     return TZ_OK;
 }
 

@@ -41,6 +41,11 @@ def target_tensors(targets, n, rng=None):
 class Trainer:
     """Net + Adam optimizer of learn::main (learn/src/main.rs:100-110) on one GPU."""
 
+    # the variables of net5's RND predictor (net5.rs:114-148): trained by the step while rnd_enable() is on, and then
+    # readable / writable through tensor() like the names of `names`
+    RND_NAMES = tuple("rnd_learning.%s.%s" % (layer, part) for layer in ("input_linear", "hidden_linear", "final_linear")
+                      for part in ("weight", "bias"))
+
     def __init__(self, arch=api.ARCH_NET5, n=0, blocks=0, batch=BATCH_SIZE, lr=LEARNING_RATE, device=0):
         from . import weights as W
 
@@ -111,9 +116,57 @@ class Trainer:
         check(self.lib.tz_trainer_to_net(self.h, net.h))
 
     def tensor(self, name, what=PARAM):
+        if name in self.RND_NAMES:
+            shape = self._rnd_shape(name)
+            out = np.zeros(shape, np.float32)
+            check(self.lib.tz_trainer_get_tensor(self.h, name.encode(), what, out.ctypes.data, out.size))
+            return out
         out = np.zeros(self.names[name], np.float32)
         check(self.lib.tz_trainer_get_tensor(self.h, name.encode(), what, out.ctypes.data, out.size))
         return out.reshape(self.shapes.get(name, out.shape))
+
+    def _rnd_shape(self, name):
+        from . import weights as W
+
+        _net, layer, part = name.split(".")
+        cin = W.input_channels(self.n) * self.n * self.n
+        out, inp = {"input_linear": (W.RND_HIDDEN, cin), "hidden_linear": (W.RND_HIDDEN, W.RND_HIDDEN),
+                    "final_linear": (W.RND_OUT, W.RND_HIDDEN)}[layer]
+        return (out, inp) if part == "weight" else (out,)
+
+    def set_tensor(self, name, data, what=PARAM):
+        """One trained variable (a name of `names`, or of RND_NAMES while RND training is enabled) in the reference's layout."""
+        data = np.ascontiguousarray(data, np.float32)
+        check(self.lib.tz_trainer_set_tensor(self.h, name.encode(), what, data.ctypes.data, data.size))
+
+    def rnd_enable(self, on=True):
+        """tz_trainer_rnd_enable: the step also trains net5's RND predictor (loss_rnd, learn/src/main.rs:404-405)."""
+        check(self.lib.tz_trainer_rnd_enable(self.h, 1 if on else 0))
+        return self
+
+    def rnd_last(self):
+        """(loss_rnd, forward_rnd [batch]) of the last step, before that step's update."""
+        loss, raw = C.c_float(), np.zeros(self.batch, np.float32)
+        check(self.lib.tz_trainer_rnd_last(self.h, C.byref(loss), raw.ctypes.data))
+        return float(loss.value), raw
+
+    def rnd_activation(self, which, layer):
+        """What the last RND forward left in MLP `which` (0 learning, 1 target): layer 0 / 1 after the ReLU [batch, 1024],
+        2 the output [batch, 512]."""
+        from . import weights as W
+
+        out = np.zeros((self.batch, W.RND_OUT if layer == 2 else W.RND_HIDDEN), np.float32)
+        check(self.lib.tz_trainer_rnd_activation(self.h, which, layer, out.ctypes.data, out.size))
+        return out
+
+    def rnd_calibrate(self, early, late, apply=True):
+        """update_rnd (learn/src/rnd_normalization.rs:74-78): (min over the early states, max over the late ones); with
+        `apply` they become the variables min / max."""
+        e, l = api._states(early), api._states(late)
+        mn, mx = C.c_float(), C.c_float()
+        check(self.lib.tz_trainer_rnd_calibrate(self.h, e.ctypes.data, len(e), l.ctypes.data, len(l), 1 if apply else 0,
+                                                C.byref(mn), C.byref(mx)))
+        return float(mn.value), float(mx.value)
 
     def extras(self):
         """The variables the step never touches (RND nets, SimHash matrix), as the library carries them."""
@@ -271,6 +324,14 @@ def pre_training(trainer, mcts, rng_seed, directory=None, initial_targets=INITIA
     return losses
 
 
+def rnd_reference(mcts, seed=0, n_early=256, early_ply=4, n_late=256, late_ply=120):
+    """reference_games (learn/src/rnd_normalization.rs:23-58) through tz_learn_rnd_reference: (early, late) state arrays.
+    `mcts`: a BatchedMCTS of any agent kind; its positions are overwritten."""
+    early, late = np.zeros(n_early, api.STATE_DTYPE), np.zeros(n_late, api.STATE_DTYPE)
+    check(_lib.load().tz_learn_rnd_reference(mcts.h, seed, n_early, early_ply, n_late, late_ply, early.ctypes.data, late.ctypes.data))
+    return early, late
+
+
 def save_model(trainer, path, hash_net=None, background=None):
     """Network::save (network/mod.rs:16-18; net6_simhash.rs:152-171 also writes bitvec.bin beside the model).  The
     weights are read back from the GPU here; with `background` (a runner.AsyncAppender) the archive itself is written
@@ -293,9 +354,11 @@ def run_learn(directory, trainer, half_komi=4, steps=None, seed=0, pre_train_mct
               steps_before_reanalyze=STEPS_BEFORE_REANALYZE, steps_per_save=STEPS_PER_SAVE,
               steps_per_checkpoint=STEPS_PER_CHECKPOINT, pre_training_steps=PRE_TRAINING_STEPS,
               initial_targets=INITIAL_RANDOM_TARGETS, restart_targets=None, read_interval=10.0, sleep=30.0,
-              max_wait=None, log=None):
+              max_wait=None, log=None, train_rnd=False, rnd_reference=None, rnd_calibrate_every=0):
     """learn::main (:99-270).  `trainer` must already hold initial weights (Net::new) unless the directory has a
-    model_<steps>.ot to resume from.  Returns the number of training steps the model has seen."""
+    model_<steps>.ot to resume from.  Returns the number of training steps the model has seen.
+    train_rnd: the steps of the main loop also train the RND predictor (:404-405); rnd_reference = (early, late) states: update_rnd
+    (:415-416) runs before every model file written from then on and every rnd_calibrate_every steps (0: only before files)."""
     import os
     import time
 
@@ -304,6 +367,11 @@ def run_learn(directory, trainer, half_komi=4, steps=None, seed=0, pre_train_mct
     from .runner import AsyncAppender
 
     n, rng = trainer.n, np.random.default_rng([seed, 5])
+
+    def calibrate():
+        if train_rnd and rnd_reference is not None:
+            trainer.rnd_calibrate(rnd_reference[0], rnd_reference[1], apply=True)
+
     saver = AsyncAppender()   # model files are written behind the training loop, in order
     resume = model_path_with_most_steps(directory)
     if resume is not None:
@@ -332,6 +400,9 @@ def run_learn(directory, trainer, half_komi=4, steps=None, seed=0, pre_train_mct
             pre_training(trainer, pre_train_mcts, seed, directory, initial_targets, pre_training_steps, log)
             starting_steps += pre_training_steps
             save_model(trainer, os.path.join(directory, "model_%07d.ot" % starting_steps), hash_net)
+    if train_rnd:
+        trainer.rnd_enable(True)
+    calibrate()
     save_model(trainer, os.path.join(directory, "model_latest.ot"), hash_net)
     exploitation = TargetBuffer(n, half_komi, SELFPLAY_TARGET_FORCED_USES)
     reanalyze = TargetBuffer(n, half_komi, REANALYZE_TARGET_FORCED_USES)
@@ -350,6 +421,9 @@ def run_learn(directory, trainer, half_komi=4, steps=None, seed=0, pre_train_mct
             hash_net.hash_indices(states, update=True)  # net.update_counts(&tensors.input), :418
         if log:
             log("step %d: loss_policy %.5f loss_value %.5f loss_ube %.5f" % ((step_no,) + losses))
+        if step_no % steps_per_save == 0 or step_no % steps_per_checkpoint == 0 or (
+                rnd_calibrate_every > 0 and step_no % rnd_calibrate_every == 0):
+            calibrate()
         if step_no % steps_per_save == 0:
             save_model(trainer, os.path.join(directory, "model_latest.ot"), hash_net, saver)
         if step_no % steps_per_checkpoint == 0:
@@ -435,6 +509,15 @@ class NativeLearnLoop:
         check(self.lib.tz_learn_step(self.h, 1 if using_reanalyze else 0, 1 if train_ube else 0, 1 if augment else 0, losses.ctypes.data))
         return tuple(float(x) for x in losses)
 
+    def set_rnd(self, train_rnd=True, early=None, late=None, calibrate_every=0):
+        """tz_learn_set_rnd: every step of the loop trains the RND predictor; with reference positions, run() calibrates min / max
+        before every model file it writes itself and every `calibrate_every` steps."""
+        e = api._states(early) if early is not None else np.zeros(0, api.STATE_DTYPE)
+        l = api._states(late) if late is not None else np.zeros(0, api.STATE_DTYPE)
+        check(self.lib.tz_learn_set_rnd(self.h, 1 if train_rnd else 0, e.ctypes.data if len(e) else None, len(e),
+                                        l.ctypes.data if len(l) else None, len(l), calibrate_every))
+        return self
+
     def last_batch(self):
         B, out = self.trainer.batch, api.policy_size(self.trainer.n)
         states = np.zeros(B, api.STATE_DTYPE)
@@ -477,10 +560,14 @@ def run_learn_native(directory, trainer, half_komi=4, steps=None, seed=0, pre_tr
                      min_selfplay=MIN_SELFPLAY_BUFFER_LEN, min_reanalyze=MIN_REANALYZE_BUFFER_LEN,
                      steps_before_reanalyze=STEPS_BEFORE_REANALYZE, steps_per_save=STEPS_PER_SAVE,
                      steps_per_checkpoint=STEPS_PER_CHECKPOINT, pre_training_steps=PRE_TRAINING_STEPS,
-                     initial_targets=INITIAL_RANDOM_TARGETS, read_interval=10.0, sleep=30.0, max_wait=None, log=None):
+                     initial_targets=INITIAL_RANDOM_TARGETS, read_interval=10.0, sleep=30.0, max_wait=None, log=None,
+                     train_rnd=False, rnd_reference=None, rnd_calibrate_every=0):
     """learn::main (learn/src/main.rs:99-270) with the buffers, batch construction and loop in native code; this function
     keeps what touches files in the reference's formats through host tools: model discovery / resume and the save
-    points (LibTorch archives)."""
+    points (LibTorch archives).
+    train_rnd: the steps of the main loop also train the RND predictor (:404-405); rnd_reference = (early, late) states
+    (rnd_reference() makes them): update_rnd (:415-416) runs before every model file written from then on and every
+    rnd_calibrate_every steps (0: only before files)."""
     import os
 
     from . import ot
@@ -514,14 +601,23 @@ def run_learn_native(directory, trainer, half_komi=4, steps=None, seed=0, pre_tr
                 pre.close()
                 starting_steps += pre_training_steps
                 save_model(trainer, os.path.join(directory, "model_%07d.ot" % starting_steps), hash_net)
-        save_model(trainer, os.path.join(directory, "model_latest.ot"), hash_net)
         loop = NativeLearnLoop(trainer, half_komi, seed)
+        have_reference = train_rnd and rnd_reference is not None
+        if train_rnd:
+            # the native loop calibrates on the multiples of rnd_calibrate_every; the files are written here, so is their calibration
+            loop.set_rnd(True, rnd_reference[0] if have_reference else None, rnd_reference[1] if have_reference else None,
+                         rnd_calibrate_every)
+        if have_reference:
+            trainer.rnd_calibrate(rnd_reference[0], rnd_reference[1], apply=True)
+        save_model(trainer, os.path.join(directory, "model_latest.ot"), hash_net)
 
         def on_step(step_no, losses, states):
             if hash_net is not None:
                 hash_net.hash_indices(states, update=True)
             if log:
                 log("step %d: loss_policy %.5f loss_value %.5f loss_ube %.5f" % ((step_no,) + tuple(losses)))
+            if have_reference and (step_no % steps_per_save == 0 or step_no % steps_per_checkpoint == 0):
+                trainer.rnd_calibrate(rnd_reference[0], rnd_reference[1], apply=True)
             if step_no % steps_per_save == 0:
                 save_model(trainer, os.path.join(directory, "model_latest.ot"), hash_net, saver)
             if step_no % steps_per_checkpoint == 0:

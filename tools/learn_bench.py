@@ -1,5 +1,6 @@
 """Times the learn step at the reference's configuration: net5, 20 blocks, batch 128
-(learn/src/main.rs:43).  `python tools/learn_bench.py [steps] [batch]`.  The CPU figure quoted beside it comes from
+(learn/src/main.rs:43).  `python tools/learn_bench.py [steps] [batch] [--rnd]`; --rnd: the same timing with the RND predictor
+trained in the step (tz_trainer_rnd_enable; 17.5 MFLOP more per position).  The CPU figure quoted beside it comes from
 tests/learn_cpu_time.py (the PyTorch fp32 restatement is test infrastructure and is not imported here)."""
 import json
 import os
@@ -23,6 +24,9 @@ def main():
     n = 5
     w = W.init_weights(W.ARCH_NET5, seed=123)
     tr = L.Trainer(arch=A.ARCH_NET5, batch=B).load_tensors(w)
+    rnd = "--rnd" in sys.argv
+    if rnd:
+        tr.rnd_enable()
     dummy = A.BatchedMCTS(B, n, 4, agent_kind=A.AGENT_DUMMY, node_capacity=1 << 10)
     from takzero_amd.selfplay import SelfPlay
 
@@ -37,9 +41,13 @@ def main():
     for _ in range(steps):
         losses = tr.step(*tensors, train_ube=True)
     dt = (time.perf_counter() - t0) / steps
-    flop = 3 * 1.1975e9 * B  # forward + data gradient + weight gradient of every conv / linear (RND is not trained)
+    flop = 3 * 1.1975e9 * B  # forward + data gradient + weight gradient of every conv / linear of the trunk and heads
+    if rnd:   # two MLP forwards, the predictor's weight gradients and two data gradients
+        flop += 2 * B * (2 * 2 * (800 * 1024 + 1024 * 1024 + 1024 * 512) + 1024 * 1024 + 1024 * 512)
     line = {"metric": "learn steps/s", "value": 1.0 / dt, "ms_per_step": dt * 1e3, "batch": B, "positions_per_s": B / dt,
-            "tflops": flop / dt / 1e12, "losses": losses, "dtype": "f32"}
+            "tflops": flop / dt / 1e12, "losses": losses, "dtype": "f32", "train_rnd": rnd}
+    if rnd:
+        line["loss_rnd"] = tr.rnd_last()[0]
     if "--loop" in sys.argv:
         # learn::main end to end: target file tailing, sampling with forced uses, augmentation, dense tensors, step,
         # model files every 100 steps — on a directory holding 20 000 random-game targets
@@ -58,7 +66,7 @@ def main():
         line["loop_driver"] = "native" if "--native" in sys.argv else "python"
         run(d, tr, steps=loop_steps, seed=1, pre_train_mcts=None, min_selfplay=10000,
                     steps_before_reanalyze=10 ** 9, read_interval=10.0, sleep=0.01, max_wait=60,
-                    log=lambda msg: stamps.append(time.perf_counter()))
+                    log=lambda msg: stamps.append(time.perf_counter()), train_rnd=rnd)
         dt_loop = (stamps[-1] - stamps[49]) / (len(stamps) - 50)   # steady state: after start-up saves and the first read
         import numpy as _np
 
