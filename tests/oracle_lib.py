@@ -128,6 +128,7 @@ def load():
     lib.tzo_search_step.argtypes = [C.c_void_p, C.c_void_p]
     lib.tzo_search_restart_terminal.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.tzo_search_gumbel_sh.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.tzo_search_terminal_details.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.tzo_search_counters.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.tzo_search_replay.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     lib.tzo_kat_find_tinue.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_float,
@@ -298,6 +299,12 @@ class OracleSearch:
         out = np.zeros(self.batch, np.int8)
         self.lib.tzo_search_restart_terminal(self.h, choice.ctypes.data, out.ctypes.data)
         return out
+
+    def terminal_details(self):
+        """Mirror of BatchedMCTS.terminal_details: reason and winner of the games the last restart_terminal found finished."""
+        reason, winner = np.zeros(self.batch, np.int8), np.zeros(self.batch, np.uint8)
+        assert self.lib.tzo_search_terminal_details(self.h, reason.ctypes.data, winner.ctypes.data) == 0
+        return reason, winner
 
     def gumbel_sh(self, betas, k, budget, gumbel):
         betas = np.ascontiguousarray(betas, dtype=np.float32)
