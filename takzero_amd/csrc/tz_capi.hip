@@ -29,7 +29,7 @@ struct tz_search {
     // ~60 launches per simulation would otherwise leave the GPU waiting for the host
     hipGraphExec_t graph[2] = {nullptr, nullptr};
     int warm[2] = {0, 0};
-    uint64_t graph_gen[2] = {0, 0};  // tz_net::weights_gen the graph was captured with
+    uint64_t graph_gen[2] = {0, 0};  // tz_net::capture_gen the graph was captured with
     bool use_graph = true;
     uint64_t sim_index = 0;
     // tz_search_simulate_batch: leaf slots, allocated at first use and grown on demand
@@ -108,8 +108,9 @@ int one_simulation(tz_search* s, bool from_start) {
         s->warm[gi]++;
         return one_simulation_eager(s, from_start, sample);
     }
-    if (s->graph[gi] && s->net && s->graph_gen[gi] != s->net->weights_gen) {
-        // hot reload (selfplay/src/main.rs:107-110): the captured launches point at the old weights
+    if (s->graph[gi] && s->net && s->graph_gen[gi] != s->net->capture_gen) {
+        // tz_net_invalidate_captures: a hot reload (selfplay/src/main.rs:107-110), grown work buffers or a new SimHash set;
+        // the captured launches point at what was replaced
         (void)hipGraphExecDestroy(s->graph[gi]);
         s->graph[gi] = nullptr;
     }
@@ -126,7 +127,7 @@ int one_simulation(tz_search* s, bool from_start) {
         const hipError_t ei = hipGraphInstantiate(&s->graph[gi], g, nullptr, nullptr, 0);
         (void)hipGraphDestroy(g);
         if (ei != hipSuccess) return tz_fail(TZ_EDEVICE, std::string("hipGraphInstantiate: ") + hipGetErrorString(ei));
-        s->graph_gen[gi] = s->net ? s->net->weights_gen : 0;
+        s->graph_gen[gi] = s->net ? s->net->capture_gen : 0;
     }
     TZ_HIP(hipGraphLaunch(s->graph[gi], s->stream));
     return TZ_OK;
@@ -219,11 +220,7 @@ int ensure_leaf_batch(tz_search* s, int leaves) {
         s->lb_slots = slots;
     }
     s->lb.leaves = leaves;
-    if (s->net && (int)slots > s->net->max_batch) {
-        int rc = tz_net_ensure_batch(s->net, (int)slots);
-        if (rc) return rc;
-        s->net->weights_gen++;  // the captured lock-step graphs of every handle on this net point at the buffers just replaced
-    }
+    if (s->net) return tz_net_ensure_batch(s->net, (int)slots);  // growing invalidates the captured lock-step graphs
     return TZ_OK;
 }
 

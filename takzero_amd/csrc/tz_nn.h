@@ -22,7 +22,7 @@ struct tz_net {
     int cin = 0, cin_pad = 0, pol_ch = 0, pol_stride = 0, ppt = 0;
     bool loaded = false, has_rnd = false, has_hash = false;
     TensorStore store;         // host copy of the VarStore (fp32, `.a.` / `.b.` names): tz_net_save / clone / load_partial
-    uint64_t weights_gen = 0;  // bumped by every successful load: captured graphs hold weight pointers
+    uint64_t capture_gen = 0;  // tz_net_invalidate_captures: bumped whenever something a captured simulation names is replaced
     ConvW conv_in, policy;
     std::vector<ConvW> res;  // 2 per block
     uint16_t* tower_w = nullptr;  // all residual-tower layers back to back (fused tower kernel)
@@ -70,6 +70,10 @@ struct tz_net {
 };
 
 int tz_net_ensure_batch(tz_net* net, int batch);
+// Marks the captured simulation graphs of every search handle on this net as stale.  A capture holds, by value, the weights,
+// the work buffers and the SimHash set: whatever frees or replaces one of them calls this, and one_simulation (tz_capi.hip)
+// drops a graph of an older generation and captures again.
+void tz_net_invalidate_captures(tz_net* net);
 // Evaluate `count` positions: slot i reads states_dev[game_index_dev ? game_index_dev[i] : i].
 // If count_dev is non-null the number of valid slots is read on the device (<= max_positions).
 int tz_net_forward_device(tz_net* net, const tz_state* states_dev, const int32_t* game_index_dev,

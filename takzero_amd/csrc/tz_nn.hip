@@ -3710,10 +3710,14 @@ int tz_nn_encode_planes(int n, int cin, const tz_state* states_dev, int count, f
 }
 
 // ---------------------------------------------------------------------------------------------
+void tz_net_invalidate_captures(tz_net* net) { net->capture_gen++; }
+
 int tz_net_ensure_batch(tz_net* net, int batch) {
     if (batch <= net->max_batch) return TZ_OK;
     TZ_HIP(hipSetDevice(net->device));
     TZ_HIP(hipStreamSynchronize(net->stream));
+    tz_net_invalidate_captures(net);  // the captured simulations of every handle on this net name the buffers freed below
+    net->max_batch = 0;               // ... and nothing may run on them if an allocation below fails
     void** bufs[] = {&net->act_a, &net->act_b, &net->act_c, (void**)&net->planes, (void**)&net->policy_out,
                      (void**)&net->value, (void**)&net->ube, (void**)&net->variance, (void**)&net->aux,
                      &net->rnd_in, &net->rnd_h1, &net->rnd_h2, (void**)&net->rnd_out, &net->seeds};
@@ -4045,7 +4049,7 @@ static int net_commit_pending(tz_net* net, tz_pending_weights* p) {
     free_weights(old);
     net->store = std::move(p->store);
     net->loaded = true;
-    net->weights_gen++;
+    tz_net_invalidate_captures(net);  // hot reload: the captured launches point at the old weights
     delete p;
     return TZ_OK;
 }
@@ -4357,6 +4361,7 @@ int tz_net_broadcast(tz_net* net, tz_comm* c, int root, int status) {
             return rc;
         }
         TZ_HIP(hipStreamSynchronize(net->stream));
+        tz_net_invalidate_captures(net);
         (void)hipFree(net->bitset);
         net->bitset = staging;
     }
@@ -4779,6 +4784,7 @@ int tz_net_load_bitset(tz_net* net, const char* path) {
         return tz_fail(TZ_EPARSE, "tz_net_load_bitset: file is not 2^32 bits");
     }
     TZ_HIP(hipStreamSynchronize(net->stream));
+    tz_net_invalidate_captures(net);
     (void)hipFree(net->bitset);
     net->bitset = staging;
     return TZ_OK;

@@ -58,10 +58,13 @@ struct Search {
     std::vector<TakEnv> envs;
     std::unique_ptr<Agent<TakEnv>> agent;
     uint64_t counts[N_COUNTS] = {0, 0, 0, 0, 0};
+    std::vector<uint32_t> round_leaves;  // per tree: the leaves it collected in its latest simulate_batch round
 };
 
 // mcts.rs:268-328, line for line
-void simulate_batch(Search& s, Node<TakEnv>& root, const TakEnv& env, float beta, size_t batch_size) {
+void simulate_batch(Search& s, size_t game, float beta, size_t batch_size) {
+    Node<TakEnv>& root = s.nodes[game];
+    const TakEnv& env = s.envs[game];
     std::vector<std::vector<size_t>> trajectories;
     std::vector<std::vector<int>> actionss;
     std::vector<TakEnv> envs;
@@ -84,6 +87,7 @@ void simulate_batch(Search& s, Node<TakEnv>& root, const TakEnv& env, float beta
         if (trajectories.size() == batch_size) break;                   // :297
     }
     s.counts[LEAVES] += trajectories.size();
+    s.round_leaves[game] = (uint32_t)trajectories.size();
     if (trajectories.size() < batch_size) s.counts[SHORT_ROUNDS]++;
     if (trajectories.empty()) return;                                   // :303
     std::vector<std::vector<float>> logits;
@@ -120,6 +124,7 @@ Search* sbr_create(int agent_kind, sbr_agent_fn fn, void* user, int batch, int n
     s->half_komi = half_komi;
     s->nodes.resize(batch);
     s->envs.resize(batch);
+    s->round_leaves.assign(batch, 0);
     for (auto& e : s->envs) e.g = Game(n, half_komi);
     if (agent_kind == TZ_AGENT_DUMMY) s->agent.reset(new DummyAgent<TakEnv>());
     else if (agent_kind == TZ_AGENT_SIMPLE) s->agent.reset(new SimpleAgent());
@@ -154,7 +159,45 @@ int sbr_new_openings(Search* s, const int32_t* choice) {
 int sbr_simulate_batch(Search* s, const float* betas, int leaves, int rounds) {
     if (leaves < 1 || rounds < 0) return -1;
     for (int r = 0; r < rounds; r++)
-        for (size_t g = 0; g < s->nodes.size(); g++) simulate_batch(*s, s->nodes[g], s->envs[g], betas[g], (size_t)leaves);
+        for (size_t g = 0; g < s->nodes.size(); g++) simulate_batch(*s, g, betas[g], (size_t)leaves);
+    return 0;
+}
+
+// BatchedMCTS::simulate (batched.rs:63-128), `n_sims` times: one forward per tree, one agent call for the leaves of all trees, in
+// tree order, then the backward passes.  A forward counts as a forward and a leaf as a leaf, as the device's counters count them.
+int sbr_simulate(Search* s, const float* betas, int n_sims) {
+    if (n_sims < 0) return -1;
+    for (int r = 0; r < n_sims; r++) {
+        std::vector<size_t> games;
+        std::vector<std::vector<size_t>> trajectories;
+        std::vector<std::vector<int>> actionss;
+        std::vector<TakEnv> envs;
+        for (size_t g = 0; g < s->nodes.size(); g++) {
+            std::vector<size_t> trajectory;
+            TakEnv e = s->envs[g];
+            Eval known;
+            s->counts[FORWARDS]++;
+            if (s->nodes[g].forward(trajectory, e, betas[g], known) == Node<TakEnv>::KNOWN) {
+                s->nodes[g].backward_known_eval(trajectory, 0, known);
+                continue;
+            }
+            std::vector<int> actions;
+            e.populate_actions(actions);
+            games.push_back(g);
+            trajectories.push_back(std::move(trajectory));
+            actionss.push_back(std::move(actions));
+            envs.push_back(e);
+        }
+        s->counts[LEAVES] += games.size();
+        if (games.empty()) continue;
+        std::vector<std::vector<float>> logits;
+        std::vector<float> value, variance, probs;
+        s->agent->policy_value_uncertainty(envs, actionss, logits, value, variance);
+        for (size_t i = 0; i < games.size(); i++) {
+            softmax(logits[i], probs);
+            s->nodes[games[i]].backward_network_eval(trajectories[i], 0, actionss[i], logits[i], probs, value[i], variance[i]);
+        }
+    }
     return 0;
 }
 
@@ -171,6 +214,8 @@ int sbr_step(Search* s, const uint16_t* actions) {
 // per-call event counts since creation: forwards made, Known results inside a round, leaves collected, leaves already collected
 // earlier in the same round, (tree, round) pairs that ended short of `leaves`
 void sbr_counts(Search* s, uint64_t* out) { memcpy(out, s->counts, sizeof s->counts); }
+// per tree, the leaves collected in the latest simulate_batch round: what the device's offset[] and index[] are built from
+void sbr_round_leaves(Search* s, uint32_t* out) { memcpy(out, s->round_leaves.data(), s->round_leaves.size() * sizeof(uint32_t)); }
 
 static size_t tree_size(const Node<TakEnv>& node) {
     size_t n = 1;

@@ -28,8 +28,10 @@ def build(out_dir):
     lib.sbr_set_positions.argtypes = [vp, ci, vp, vp]
     lib.sbr_new_openings.argtypes = [vp, vp]
     lib.sbr_simulate_batch.argtypes = [vp, vp, ci, ci]
+    lib.sbr_simulate.argtypes = [vp, vp, ci]
     lib.sbr_step.argtypes = [vp, vp]
     lib.sbr_counts.argtypes = [vp, vp]
+    lib.sbr_round_leaves.argtypes = [vp, vp]
     lib.sbr_principal_variation.argtypes = [vp, ci, vp, ci]
     lib.sbr_tree_size.restype = C.c_uint64
     lib.sbr_tree_size.argtypes = [vp, ci]
@@ -66,6 +68,11 @@ class RefSearch:
         betas = np.ascontiguousarray(betas, dtype=np.float32)
         assert self.lib.sbr_simulate_batch(self.h, betas.ctypes.data, leaves, rounds) == 0
 
+    def simulate(self, betas, n_sims=1):
+        """lock-step BatchedMCTS::simulate on the same trees"""
+        betas = np.ascontiguousarray(betas, dtype=np.float32)
+        assert self.lib.sbr_simulate(self.h, betas.ctypes.data, n_sims) == 0
+
     def step(self, actions):
         actions = np.ascontiguousarray(actions, dtype=np.uint16)
         self.lib.sbr_step(self.h, actions.ctypes.data)
@@ -74,6 +81,12 @@ class RefSearch:
         out = np.zeros(len(COUNT_NAMES), np.uint64)
         self.lib.sbr_counts(self.h, out.ctypes.data)
         return dict(zip(COUNT_NAMES, (int(x) for x in out)))
+
+    def round_leaves(self):
+        """per tree, the leaves it collected in the latest simulate_batch round"""
+        out = np.zeros(self.batch, np.uint32)
+        self.lib.sbr_round_leaves(self.h, out.ctypes.data)
+        return out
 
     def tree_size(self, game):
         return int(self.lib.sbr_tree_size(self.h, game))
@@ -114,8 +127,10 @@ def same_node(a, b, where):
         assert np.array_equal(bits(ca[k]), bits(cb[k])), (where, k)
 
 
-def compare(dev, ref, where=""):
+def compare(dev, ref, where="", deep=None):
     """The root, all its children, every node to depth 2, every node along the principal variation, and the PV itself.
+    `deep` lists the trees walked below the root and along the PV (all trees when None); the root and all its children are
+    compared on every tree.
     A node query returns the node and the statistics of all its children, so the queries of the root and of every depth-1 node
     cover every node to depth 2; the depth-2 nodes that were visited are queried too, for their child lists (an unvisited node
     has none).  dev.node and ref.node have the same signature (api.BatchedMCTS.node / RefSearch.node or OracleSearch.node)."""
@@ -124,6 +139,8 @@ def compare(dev, ref, where=""):
         root = ref.node(g, [])
         same_node(dev.node(g, []), root, (where, g, "root"))
         nodes += 1
+        if deep is not None and g not in deep:
+            continue
         for m1 in root[1]["move_idx"]:
             n1 = ref.node(g, [m1])
             same_node(dev.node(g, [m1]), n1, (where, g, int(m1)))
@@ -140,3 +157,59 @@ def compare(dev, ref, where=""):
                 same_node(dev.node(g, pv[:d]), ref.node(g, pv[:d]), (where, g, "pv", d))
                 nodes += 1
     return nodes
+
+
+# ---- starts of the wide cases (tests/test_gpu_simulate_batch_wide.py; tests/test_simulate_batch_ref.py holds their preconditions)
+WIDE_TREES = (0, 63, 64, 65, 1023, 1024, 1025)      # either side of a wave of 64 trees and of compact_batch_kernel's 1024-tree chunk
+
+
+def deep_trees(batch):
+    """the trees a wide case walks in depth: WIDE_TREES where they exist, and the last tree"""
+    return sorted({g for g in WIDE_TREES if g < batch} | {batch - 1})
+
+
+def finished_position(oracle, n, half_komi, seed):
+    """the end of a random playout: a tree started here collects nothing"""
+    return playout(oracle, n, half_komi, seed)[-1]
+
+
+def playout(oracle, n, half_komi, seed):
+    """every position of one random game, the finished one last"""
+    rng = np.random.default_rng(seed)
+    s = O.state_default(oracle, n, half_komi)
+    out = [s]
+    while oracle.tzo_terminal(C.byref(s)) == -1:
+        mv = O.possible_moves(oracle, s)
+        s = O.play(oracle, s, mv[int(rng.integers(len(mv)))])
+        out.append(s)
+    return out
+
+
+def mixed_starts(oracle, batch, n, half_komi, seed):
+    """Starts by tree index: g % 3 == 0 a fresh opening (the returned choice, applied by new_openings), g % 3 == 1 the finished
+    position of a random playout (collects nothing), g % 3 == 2 a position one to three plies before the end of one (Known results
+    inside its rounds end them short).  Returns (choice for new_openings, tree indices, states for set_positions)."""
+    games = [playout(oracle, n, half_komi, seed * 1000 + k) for k in range(96)]
+    choice = (np.arange(batch) * 3 + 1).astype(np.int32) % 16
+    idx, states = [], []
+    for g in range(batch):
+        game = games[(g // 3) % len(games)]
+        if g % 3 == 1:
+            idx.append(g)
+            states.append(game[-1])
+        elif g % 3 == 2:
+            idx.append(g)
+            states.append(game[max(0, len(game) - 2 - (g // 3) % 3)])
+    return choice, np.array(idx, np.int32), states
+
+
+def apply_starts(search, starts):
+    choice, idx, states = starts
+    search.new_openings(choice)
+    search.set_positions(idx, O.states_array(states))
+
+
+def ragged(round_leaves, leaves):
+    """does one round hold a tree without a leaf, a tree with some and a tree with all of them"""
+    r = np.asarray(round_leaves)
+    return bool((r == 0).any() and ((r > 0) & (r < leaves)).any() and (r == leaves).any())

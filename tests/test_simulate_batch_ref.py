@@ -58,6 +58,58 @@ def test_root_visits_grow_by_the_forwards_made(ref_lib, leaves):
     assert c["duplicate_leaves"] >= leaves - 1, c      # the first round stops `leaves` times at the fresh root
 
 
+@pytest.mark.parametrize("agent", [1, 2])
+def test_lock_step_simulate_of_the_restatement_is_the_oracle_search(ref_lib, agent):
+    """sbr_simulate (the lock-step calls of tests/test_gpu_simulate_batch_wide.py's last case) against BatchedMCTS::simulate of the
+    pinned oracle: several games, one of them finished, root and children of every game and depth 2, and the same event counts"""
+    oracle = O.load()
+    B, n = 4, 4
+    starts = [U.finished_position(oracle, n, 4, 5)]
+    ref = U.RefSearch(ref_lib, B, n, 4, agent_kind=agent)
+    ora = O.OracleSearch(oracle, B, n, 4, agent_kind=agent)
+    for s in (ref, ora):
+        s.new_openings([1, 4, 7, 10])
+        s.set_positions([2], starts)
+    betas = np.array([0.0, 0.25, 0.0, 0.5], np.float32)
+    for sims in (1, 40):
+        ref.simulate(betas, sims)
+        ora.simulate(betas, sims)
+
+    class NoPv:
+        batch = B
+        node = staticmethod(ora.node)
+
+    assert U.compare(ref, NoPv, "lock-step") > 50
+    c = ref.counts()
+    assert (c["forwards"], c["leaves"]) == ora.counters() and c["leaves"] < c["forwards"] == 41 * B, (c, ora.counters())
+
+
+@pytest.mark.parametrize("agent", [1, 2])
+def test_the_wide_start_mix_gives_ragged_rounds(ref_lib, agent):
+    """The preconditions of the 1100-tree case of tests/test_gpu_simulate_batch_wide.py, with its seed, without a GPU: in one round
+    some tree collects nothing, some tree between 1 and leaves - 1, some tree all of its leaves; finished starts collect nothing; and the trees walked in depth are the
+    ones on either side of the 64-tree and 1024-tree boundaries."""
+    from test_gpu_simulate_batch_wide import WIDE_SEED
+
+    oracle = O.load()
+    B, n, leaves = 1100, 4, 8
+    starts = U.mixed_starts(oracle, B, n, 4, WIDE_SEED)
+    assert all(oracle.tzo_terminal(starts[2][k]) != -1 for k in range(0, len(starts[1]), 2))       # g % 3 == 1: finished
+    assert all(oracle.tzo_terminal(starts[2][k]) == -1 for k in range(1, len(starts[1]), 2))       # g % 3 == 2: still running
+    ref = U.RefSearch(ref_lib, B, n, 4, agent_kind=agent)
+    U.apply_starts(ref, starts)
+    betas = np.where(np.arange(B) % 2 == 0, 0.0, 0.25).astype(np.float32)
+    seen, total = [], 0
+    for _ in range(3):
+        ref.simulate_batch(betas, leaves, 1)
+        r = ref.round_leaves()
+        seen.append(U.ragged(r, leaves))
+        total += int(r.sum())
+        assert r.max() <= leaves and np.all(r[1::3] == 0) and total == ref.counts()["leaves"]
+    assert any(seen) and ref.counts()["short_rounds"] > 0
+    assert U.deep_trees(B) == [0, 63, 64, 65, 1023, 1024, 1025, 1099] and U.deep_trees(5) == [0, 4]
+
+
 def test_the_header_declares_both_entry_points():
     header = open(os.path.join(ROOT, "include", "takzero_hip.h")).read()
     assert re.search(r"int tz_search_simulate_batch\(tz_search\* s, const float\* betas, int leaves, int rounds\);", header)
