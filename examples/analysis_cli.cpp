@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "arch_arg.h"
 #include "selection_arg.h"
 #include "takzero_hip.h"
 
@@ -40,7 +41,7 @@ int main(int argc, char** argv) {
     int arch = TZ_ARCH_NET5, n = 5, blocks = 0, leaves = 128, rounds = 8, precision = TZ_PREC_F16, device = 0, half_komi = 4, show = 10;
     unsigned long long seed = 0;
     auto usage = []() {
-        fprintf(stderr, "usage: analysis_cli [--model FILE.ot|.tzw --tps TPS --arch 4|5|6|100 --n N --blocks K --leaves 128 --rounds 8 --selection puct|uct|improved "
+        fprintf(stderr, "usage: analysis_cli [--model FILE.ot|.tzw --tps TPS --arch 4|5|6|14|100|net4_simhash|net5|net6_simhash|net4_lcghash|test --n N --blocks K --leaves 128 --rounds 8 --selection puct|uct|improved "
                         "--half-komi 4 --children 10 --seed X --device G --f32|--bf16]\n");
         return 2;
     };
@@ -49,7 +50,7 @@ int main(int argc, char** argv) {
         auto next = [&]() -> const char* { return i + 1 < argc ? argv[++i] : ""; };
         if (a == "--model") model = next();
         else if (a == "--tps") tps = next();
-        else if (a == "--arch") arch = atoi(next());
+        else if (a == "--arch") arch = arch_from_arg(next());
         else if (a == "--n") n = atoi(next());
         else if (a == "--blocks") blocks = atoi(next());
         else if (a == "--leaves") leaves = atoi(next());
@@ -64,9 +65,7 @@ int main(int argc, char** argv) {
         else return usage();
     }
     if (selection_rule(selection) < 0) return usage();
-    if (arch == TZ_ARCH_NET5) n = 5;
-    if (arch == TZ_ARCH_NET4_SIMHASH) n = 4;
-    if (arch == TZ_ARCH_NET6_SIMHASH) n = 6;
+    if (arch_board(arch)) n = arch_board(arch);
     tz_net* net = nullptr;
     tz_search* search = nullptr;
     CHECK(tz_net_create(n, arch, device, precision, blocks, &net));

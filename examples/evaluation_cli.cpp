@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "arch_arg.h"
 #include "takzero_hip.h"
 
 #define CHECK(call)                                                        \
@@ -82,7 +83,7 @@ int main(int argc, char** argv) {
         if (a == "--model-path") model_path = next();
         else if (a == "--opening-book") book_path = next();
         else if (a == "--step") step = atoi(next());
-        else if (a == "--arch") arch = atoi(next());
+        else if (a == "--arch") arch = arch_from_arg(next());
         else if (a == "--n") n = atoi(next());
         else if (a == "--blocks") blocks = atoi(next());
         else if (a == "--games") games = atoi(next());
@@ -103,13 +104,11 @@ int main(int argc, char** argv) {
         }
     }
     if (model_path.empty()) {
-        fprintf(stderr, "usage: evaluation_cli --model-path DIR [--step K --opening-book FILE --arch 4|5|6|100 --n N --blocks K --games 64 "
+        fprintf(stderr, "usage: evaluation_cli --model-path DIR [--step K --opening-book FILE --arch 4|5|6|14|100|net4_simhash|net5|net6_simhash|net4_lcghash|test --n N --blocks K --games 64 "
                         "--sampled-actions 64 --budget 768 --max-moves 200 --rounds R --seed X --sleep SECONDS --device G --bf16|--f16c6|--f16c8|--f16x2]\n");
         return 2;
     }
-    if (arch == TZ_ARCH_NET5) n = 5;
-    if (arch == TZ_ARCH_NET4_SIMHASH) n = 4;
-    if (arch == TZ_ARCH_NET6_SIMHASH) n = 6;
+    if (arch_board(arch)) n = arch_board(arch);
     printf("seed: %llu\n", seed);
     std::mt19937_64 rng(seed);
     tz_net *a = nullptr, *b = nullptr;

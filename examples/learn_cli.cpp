@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "arch_arg.h"
 #include "takzero_hip.h"
 
 #define CHECK(call)                                                        \
@@ -61,7 +62,7 @@ static int on_step(void* user, int64_t step, const float* losses, const tz_state
 
 static const char* USAGE =
     "usage: learn_cli --directory DIR [options]\n"
-    "  --arch 4|5|6|100  --n N  --blocks K  --batch B  --steps S  --seed X\n"
+    "  --arch 4|5|6|14|100|net4_simhash|net5|net6_simhash|net4_lcghash|test  --n N  --blocks K  --batch B  --steps S  --seed X\n"
     "  --pre-training-steps S  --initial-targets T  --steps-before-reanalyze S  --min-selfplay T  --min-reanalyze T\n"
     "  --steps-per-save S  --steps-per-checkpoint S  --read-interval SEC  --sleep SEC  --wait-limit SEC  --verbose\n"
     "  --train-rnd               net5 only: train the RND predictor in every step of the main loop and calibrate min / max\n"
@@ -79,7 +80,7 @@ int main(int argc, char** argv) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return i + 1 < argc ? argv[++i] : ""; };
         if (a == "--directory") directory = next();
-        else if (a == "--arch") arch = atoi(next());
+        else if (a == "--arch") arch = arch_from_arg(next());
         else if (a == "--n") n = atoi(next());
         else if (a == "--blocks") blocks = atoi(next());
         else if (a == "--batch") batch = atoi(next());
@@ -118,13 +119,11 @@ int main(int argc, char** argv) {
         fprintf(stderr, "--rnd-calibrate-every must not be negative\n");
         return 2;
     }
-    if (arch == TZ_ARCH_NET5) n = 5;
-    if (arch == TZ_ARCH_NET4_SIMHASH) n = 4;
-    if (arch == TZ_ARCH_NET6_SIMHASH) n = 6;
-    const bool hash = arch == TZ_ARCH_NET4_SIMHASH || arch == TZ_ARCH_NET6_SIMHASH;
+    if (arch_board(arch)) n = arch_board(arch);
+    const bool hash = arch_has_set(arch);
     fprintf(stderr, "seed = %llu\n", seed);
     tz_trainer* trainer = nullptr;
-    tz_net* net = nullptr;   // Net::new for the initial variables; for SimHash nets also the set that update_counts feeds
+    tz_net* net = nullptr;   // Net::new for the initial variables; for the hash nets also the set that update_counts feeds
     CHECK(tz_trainer_create(n, arch, 0, blocks, batch, 1e-4f, &trainer));
     CHECK(tz_net_create(n, arch, 0, TZ_PREC_F16, blocks, &net));
     long long starting_steps = 0;

@@ -15,6 +15,7 @@
 #include <future>
 #include <string>
 
+#include "arch_arg.h"
 #include "selection_arg.h"
 #include "takzero_hip.h"
 
@@ -109,7 +110,7 @@ int main(int argc, char** argv) {
         else if (a == "--async-reload") async_reload = true;
         else if (a == "--search") search = next();
         else if (a == "--selection") selection = next();
-        else if (a == "--arch") arch = atoi(next());
+        else if (a == "--arch") arch = arch_from_arg(next());
         else if (a == "--n") n = atoi(next());
         else if (a == "--blocks") blocks = atoi(next());
         else if (a == "--games") games = atoi(next());
@@ -132,14 +133,12 @@ int main(int argc, char** argv) {
         }
     }
     if (directory.empty() || selection_rule(selection) < 0) {
-        fprintf(stderr, "usage: reanalyze_cli --directory DIR [--model FILE --watch model_latest.ot --arch 4|5|6|100 --n N --blocks K --games B "
+        fprintf(stderr, "usage: reanalyze_cli --directory DIR [--model FILE --watch model_latest.ot --arch 4|5|6|14|100|net4_simhash|net5|net6_simhash|net4_lcghash|test --n N --blocks K --games B "
                         "--sims S --search puct|gumbel --selection puct|uct|improved --sampled-actions K --iterations I --min-positions P --wait-limit SECONDS --seed X "
                         "--rank R --world N --device G --async-reload --bf16|--f16c6|--f16c8|--f16x2]\n");
         return 2;
     }
-    if (arch == TZ_ARCH_NET5) n = 5;
-    if (arch == TZ_ARCH_NET4_SIMHASH) n = 4;
-    if (arch == TZ_ARCH_NET6_SIMHASH) n = 6;
+    if (arch_board(arch)) n = arch_board(arch);
     if (device < 0) device = rank;
     tz_net* net = nullptr;
     tz_search* mcts = nullptr;

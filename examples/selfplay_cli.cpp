@@ -18,6 +18,7 @@
 #include <future>
 #include <string>
 
+#include "arch_arg.h"
 #include "selection_arg.h"
 #include "takzero_hip.h"
 
@@ -113,7 +114,7 @@ int main(int argc, char** argv) {
         else if (a == "--model") model = next();
         else if (a == "--search") search = next();
         else if (a == "--selection") selection = next();
-        else if (a == "--arch") arch = atoi(next());
+        else if (a == "--arch") arch = arch_from_arg(next());
         else if (a == "--n") n = atoi(next());
         else if (a == "--blocks") blocks = atoi(next());
         else if (a == "--games") games = atoi(next());
@@ -141,16 +142,14 @@ int main(int argc, char** argv) {
         }
     }
     if (directory.empty() || selection_rule(selection) < 0 || (world > 1 && comm_kind != "rccl" && comm_kind != "fs")) {
-        fprintf(stderr, "usage: selfplay_cli --directory DIR [--model FILE.ot|.tzw --watch model_latest.ot --arch 4|5|6|100 --n N --blocks K "
+        fprintf(stderr, "usage: selfplay_cli --directory DIR [--model FILE.ot|.tzw --watch model_latest.ot --arch 4|5|6|14|100|net4_simhash|net5|net6_simhash|net4_lcghash|test --n N --blocks K "
                         "--games B --sims S --search puct|gumbel --selection puct|uct|improved --sampled-actions K --moves M --exploration --async-reload --f16|--bf16|--f16c6|--f16c8|--f16x2 "
                         "--wait-limit SECONDS --seed X] [--rank R --world N --comm rccl|fs --comm-dir D --device G]\n");
         return 2;
     }
     if (device < 0) device = comm_kind == "fs" ? 0 : rank;
     if (comm_dir.empty()) comm_dir = directory;
-    if (arch == TZ_ARCH_NET5) n = 5;
-    if (arch == TZ_ARCH_NET4_SIMHASH) n = 4;
-    if (arch == TZ_ARCH_NET6_SIMHASH) n = 6;
+    if (arch_board(arch)) n = arch_board(arch);
     tz_net* net = nullptr;
     tz_search* mcts = nullptr;
     tz_selfplay* sp = nullptr;

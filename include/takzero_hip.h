@@ -89,10 +89,13 @@ typedef struct tz_state {
 typedef struct tz_net tz_net;       /* opaque: a network on one GPU  (Network + Agent impl)   */
 typedef struct tz_search tz_search; /* opaque: BatchedMCTS<B, Game<N,HALF_KOMI>> on one GPU   */
 
-/* architectures (takzero/src/network/{net4_simhash,net5,net6_simhash}.rs) */
+/* architectures (takzero/src/network/{net4_simhash,net5,net6_simhash,net4_lcghash}.rs) */
 #define TZ_ARCH_NET4_SIMHASH 4
 #define TZ_ARCH_NET5 5
 #define TZ_ARCH_NET6_SIMHASH 6
+/* the trunk, heads and 2^32-bit set of net4_simhash; the set's index is an integer hash of planes * lcghash_init
+ * (net4_lcghash.rs:202-242).  4x4 only.  Everything said about SimHash nets below holds for it. */
+#define TZ_ARCH_NET4_LCGHASH 14
 /* test architecture: same graph as net5 on any board size with configurable depth, no RND/hash */
 #define TZ_ARCH_TEST 100
 
@@ -191,8 +194,8 @@ int tz_net_encode(tz_net* net, int batch, const tz_state* states, float* planes_
 int tz_net_forward_raw(tz_net* net, int batch, const tz_state* states, float* policy_out,
                        float* value_out, float* ube_out);
 
-/* SimHash nets (net4_simhash / net6_simhash): HashNetwork::get_indices / update_counts
- * (net6_simhash.rs:202-243) and the bitvec.bin file that accompanies a model (net6_simhash.rs:152-190). */
+/* Hash nets (net4_simhash / net6_simhash / net4_lcghash): HashNetwork::get_indices / update_counts
+ * (net6_simhash.rs:202-243, net4_lcghash.rs:202-249) and the bitvec.bin file that accompanies a model (net6_simhash.rs:152-190). */
 int tz_net_hash_indices(tz_net* net, int batch, const tz_state* states, uint32_t* indices_out, int update);
 int tz_net_load_bitset(tz_net* net, const char* path);
 int tz_net_save_bitset(tz_net* net, const char* path);
@@ -529,6 +532,9 @@ int tz_device_math(int op, const float* a, const float* b, float* out, int n);
 int tz_debug_conv_bench(tz_net* net, int variant, int positions, int iters, float* ms_out);
 /* Diagnostic: the same for the fused residual-tower kernel (variant = its OPT bitmask). */
 int tz_debug_tower_bench(tz_net* net, int variant, int positions, int iters, float* ms_out);
+/* Diagnostic: average ms per launch of a hash net's index-plus-lookup kernel (simhash_state_kernel / lcghash_state_kernel) on
+ * `batch` positions, between two events around `iters` launches after two warm-up launches. */
+int tz_debug_hash_bench(tz_net* net, int batch, const tz_state* states, int iters, float* ms_out);
 /* Diagnostic (builds with --ablations, TZ_NET_ABL=8): in-kernel shader clock of the last stamped launch of the net kernel
  * (median over workgroups of delta s_memtime / delta s_memrealtime x 100 MHz) and the median duration of its tower part. */
 int tz_debug_net_clock(tz_net* net, double* mhz_out, double* tower_us_out);

@@ -921,7 +921,7 @@ struct tz_trainer {
     int sk_groups = 512;
     float* sk_ws[2] = {nullptr, nullptr};
     std::vector<void*> allocs;
-    // variables of the VarStore the trunk's step never touches (RND nets, SimHash matrix): carried through save / load.  While RND
+    // variables of the VarStore the trunk's step never touches (RND nets, SimHash matrix, lcghash_init): carried through save / load.  While RND
     // training is enabled the device holds the current rnd_learning.*; rnd_download brings them here before anything reads them.
     TensorStore extra;
     Rnd rnd;
@@ -1359,6 +1359,7 @@ int tz_trainer_create(int board_n, int arch, int device_id, int blocks, int batc
     if (arch == TZ_ARCH_NET5 && board_n != 5) return tz_fail(TZ_EINVAL, "tz_trainer_create: net5 is a 5x5 network");
     if (arch == TZ_ARCH_NET4_SIMHASH && board_n != 4) return tz_fail(TZ_EINVAL, "tz_trainer_create: net4_simhash is 4x4");
     if (arch == TZ_ARCH_NET6_SIMHASH && board_n != 6) return tz_fail(TZ_EINVAL, "tz_trainer_create: net6_simhash is 6x6");
+    if (arch == TZ_ARCH_NET4_LCGHASH && board_n != 4) return tz_fail(TZ_EINVAL, "tz_trainer_create: net4_lcghash is 4x4");
     if (batch <= 0 || batch % 64) return tz_fail(TZ_EINVAL, "tz_trainer_create: batch must be a positive multiple of 64");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev)

@@ -35,7 +35,7 @@ struct tz_net {
     uint16_t* rndw[3] = {nullptr, nullptr, nullptr};  // bf16 path: layer 1 = both nets side by side (2048 outputs),
     float* rndb[3] = {nullptr, nullptr, nullptr};     // layers 2/3 = [net][...] for grouped launches
     float rnd_min = 0.0f, rnd_max = 1.0f;
-    float* simhash = nullptr;    // [in_size][32] fp32, reference order (c*nn + px)
+    float* simhash = nullptr;    // [in_size][32] fp32, reference order (c*nn + px); TZ_ARCH_NET4_LCGHASH: lcghash_init, [in_size] in that order
     uint32_t* bitset = nullptr;  // 2^32 bits, allocated for hash archs
     // work buffers, sized for max_batch positions
     int max_batch = 0;

@@ -2721,7 +2721,91 @@ int launch_simhash_state(int n, const tz_state* states, const int32_t* gidx, con
     return TZ_OK;
 }
 
-// HashNetwork::update_counts (net6_simhash.rs:238-243): set the bit of every index
+// LCG hash straight from the packed game states (HashNetwork::get_indices, net4_lcghash.rs:202-242).  The reference multiplies the
+// planes by lcghash_init, reads each fp32 product's bits as an int32 and folds them with three nested chains acc = acc*M + 1 + v in
+// wrapping int64: over the files, over the ranks, over the channels.  Unrolled, that is
+//     H = K + sum v[c][r][f] * M^((C-1-c) + (N-1-r) + (N-1-f))   (mod 2^64),   K = the chains' increments alone,
+// a sum whose terms commute: one wave per board, lane l takes elements 7l..7l+6 of the 448 with the powers of M from a table, and a
+// 64-bit butterfly adds the lanes up.  Every plane takes part, zero planes included (0.0 * negative = -0.0 contributes -2^31), and
+// the black-to-move plane is not zeroed here.  index = |H| >> 31 (wrapping abs); H = i64::MIN, where the reference's index is out of
+// bounds, gives 0 by the 32-bit mask.
+struct LcgTable {
+    unsigned long long pow[34];   // M^e, e = 0 .. (28-1) + 3 + 3
+    unsigned long long k;         // the +1 of every step of the two outer chains (an element step's +1 travels with its element)
+};
+constexpr LcgTable lcg_table() {
+    constexpr unsigned long long M = 6364136223846793005ull;
+    LcgTable t{};
+    unsigned long long p = 1;
+    for (int e = 0; e < 34; e++) {
+        t.pow[e] = p;
+        p *= M;
+    }
+    t.k = 0;
+    for (int c = 0; c < 28; c++) {
+        t.k += t.pow[27 - c];
+        for (int r = 0; r < 4; r++) t.k += t.pow[27 - c + 3 - r];
+    }
+    return t;
+}
+__constant__ LcgTable LCG_TABLE = lcg_table();
+
+template <int NB>
+__global__ __launch_bounds__(256) void lcghash_state_kernel(const tz_state* states, const int32_t* game_index, const float* init,
+                                                            const uint32_t* bitset, const int32_t* count_dev, int count_host, int max_positions,
+                                                            float* local, uint32_t* index_out) {
+    constexpr int NN = NB * NB, CIN = 4 * NB + 12, IN = CIN * NN, BPW = 4, DW = sizeof(tz_state) / 4, PER = IN / 64;
+    static_assert(NB == 4 && IN == 64 * PER && CIN - 1 + 2 * (NB - 1) < 34, "lcghash: the table and the lane split are those of the 4x4 net");
+    __shared__ tz_state st[BPW];
+    __shared__ int fd[BPW];
+    const int count = min(count_dev ? *count_dev : count_host, max_positions);
+    const int pos0 = blockIdx.x * BPW, tid = threadIdx.x;
+    if (pos0 >= count) return;
+    const int nb = min(BPW, count - pos0);
+    for (int i = tid; i < nb * DW; i += 256) {
+        const int b = i / DW, d = i - b * DW, pos = pos0 + b;
+        reinterpret_cast<uint32_t*>(st)[i] = reinterpret_cast<const uint32_t*>(states + (game_index ? game_index[pos] : pos))[d];
+    }
+    __syncthreads();
+    if (tid < nb) fd[tid] = state_flat_diff<NB>(&st[tid]);
+    __syncthreads();
+    const int l = tid & 63, b = tid >> 6;
+    if (b >= nb) return;   // whole waves leave: the butterfly below stays within a wave
+    unsigned long long h = 0;
+#pragma unroll
+    for (int j = 0; j < PER; j++) {
+        const int k = l * PER + j, c = k / NN, px = k - c * NN, r = px / NB, f = px - r * NB;
+        const float p = plane_value<NB>(&st[b], px, c, fd[b]) * init[k];   // one IEEE multiply, nothing added: no FMA to contract
+        const long long v = (long long)__float_as_int(p);                  // view_dtype(Int), promoted by acc += x
+        h += (unsigned long long)(v + 1) * LCG_TABLE.pow[(CIN - 1 - c) + (NB - 1 - r) + (NB - 1 - f)];
+    }
+    for (int d = 32; d >= 1; d >>= 1) h += __shfl_xor(h, d);
+    if (l == 0) {
+        const long long H = (long long)(h + LCG_TABLE.k);
+        const unsigned long long a = H < 0 ? 0ull - (unsigned long long)H : (unsigned long long)H;
+        const uint32_t index = (uint32_t)((long long)a >> 31);
+        const bool seen = bitset && ((bitset[index >> 5] >> (index & 31)) & 1u);
+        local[pos0 + b] = seen ? 0.0f : 4.0f;
+        if (index_out) index_out[pos0 + b] = index;
+    }
+}
+
+int launch_lcghash_state(int n, const tz_state* states, const int32_t* gidx, const float* init, const uint32_t* bitset,
+                         const int32_t* count_dev, int count_host, int max_positions, float* local, uint32_t* index_out, hipStream_t st) {
+    if (n != 4) return tz_fail(TZ_EINVAL, "lcghash: the LCG-hash net is 4x4");
+    lcghash_state_kernel<4><<<(max_positions + 3) / 4, 256, 0, st>>>(states, gidx, init, bitset, count_dev, count_host, max_positions, local, index_out);
+    return TZ_OK;
+}
+
+// index and `local` (0 seen, 4 unseen) of every position into net->aux, by the hash of the net's architecture
+int launch_hash_state(const tz_net* net, const tz_state* states, const int32_t* gidx, const int32_t* count_dev, int count_host,
+                      int max_positions, uint32_t* index_out, hipStream_t st) {
+    if (net->arch == TZ_ARCH_NET4_LCGHASH)
+        return launch_lcghash_state(net->n, states, gidx, net->simhash, net->bitset, count_dev, count_host, max_positions, net->aux, index_out, st);
+    return launch_simhash_state(net->n, states, gidx, net->simhash, net->bitset, count_dev, count_host, max_positions, net->aux, index_out, st);
+}
+
+// HashNetwork::update_counts (net6_simhash.rs:238-243, net4_lcghash.rs:244-249): set the bit of every index
 __global__ void bitset_set_kernel(uint32_t* bitset, const uint32_t* index, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) atomicOr(&bitset[index[i] >> 5], 1u << (index[i] & 31));
@@ -3209,7 +3293,9 @@ int build_weights(tz_net* net, const TensorMap& m, NetWeights& W) {
         W.rnd_max = t1[0];
     }
     if (net->has_hash) {
-        if ((rc = get_tensor(m, "simhash_matrix", (size_t)cin * nn * 32, w))) return rc;
+        if (net->arch == TZ_ARCH_NET4_LCGHASH) rc = get_tensor(m, "lcghash_init", (size_t)cin * nn, w);
+        else rc = get_tensor(m, "simhash_matrix", (size_t)cin * nn * 32, w);
+        if (rc) return rc;
         if ((rc = upload(w, &W.simhash))) return rc;
     }
     return TZ_OK;
@@ -3906,8 +3992,7 @@ int tz_net_forward_device(tz_net* net, const tz_state* states, const int32_t* gi
             rnd_finish_kernel<<<max_positions, 64, 0, st>>>(outs[0], outs[1], net->ube, count_dev, count_host, 512, 512, net->rnd_min,
                                                             net->rnd_max, net->variance);
     } else if (net->has_hash) {
-        if ((rc = launch_simhash_state(net->n, states, gidx, net->simhash, net->bitset, count_dev, count_host, max_positions, net->aux, nullptr, st)))
-            return rc;
+        if ((rc = launch_hash_state(net, states, gidx, count_dev, count_host, max_positions, nullptr, st))) return rc;
         plain_variance_kernel<<<(max_positions + 255) / 256, 256, 0, st>>>(net->ube, net->aux, count_dev, count_host, net->variance);
     } else {
         plain_variance_kernel<<<(max_positions + 255) / 256, 256, 0, st>>>(net->ube, nullptr, count_dev, count_host, net->variance);
@@ -3936,6 +4021,7 @@ int tz_net_create(int board_n, int arch, int device_id, int precision, int block
     if (arch == TZ_ARCH_NET5) n = 5;
     else if (arch == TZ_ARCH_NET4_SIMHASH) n = 4;
     else if (arch == TZ_ARCH_NET6_SIMHASH) n = 6;
+    else if (arch == TZ_ARCH_NET4_LCGHASH) n = 4;
     else if (arch != TZ_ARCH_TEST) return tz_fail(TZ_EINVAL, "tz_net_create: unknown architecture");
     if (board_n && board_n != n) return tz_fail(TZ_EINVAL, "tz_net_create: board size does not match the architecture");
     if (n < 3 || n > 6) return tz_fail(TZ_EINVAL, "tz_net_create: board size must be 3..6");
@@ -3961,7 +4047,7 @@ int tz_net_create(int board_n, int arch, int device_id, int precision, int block
     net->pol_stride = (net->pol_ch + 127) / 128 * 128;
     net->ppt = ppt_for(n);
     net->has_rnd = arch == TZ_ARCH_NET5;
-    net->has_hash = arch == TZ_ARCH_NET4_SIMHASH || arch == TZ_ARCH_NET6_SIMHASH;
+    net->has_hash = arch == TZ_ARCH_NET4_SIMHASH || arch == TZ_ARCH_NET6_SIMHASH || arch == TZ_ARCH_NET4_LCGHASH;
     if (hipStreamCreate(&net->stream) != hipSuccess) {
         delete net;
         return tz_fail(TZ_EDEVICE, "tz_net_create: hipStreamCreate failed");
@@ -4214,7 +4300,7 @@ int tz_net_tensor_info(tz_net* net, int i, char* name_out, int name_cap, uint64_
 
 // Network::new(device, seed) (network/mod.rs:11; net5.rs:152-170): tch's default initialisers - conv / linear weights
 // Kaiming-uniform(a = sqrt 5) = U(+-1/sqrt(fan_in)), biases U(+-1/sqrt(fan_in)), BatchNorm weight U(0,1), bias 0, running
-// statistics 0 / 1, RND min 0 / max 1 (net5.rs:166-168), simhash_matrix N(0,1).  The draws come from a counter-based
+// statistics 0 / 1, RND min 0 / max 1 (net5.rs:166-168), simhash_matrix N(0,1), lcghash_init U(-100, 100).  The draws come from a counter-based
 // generator keyed by (seed, tensor name): tch's own stream (torch's Philox/mt19937 through manual_seed) is not reproduced.
 namespace {
 uint64_t mix64(uint64_t x) {
@@ -4294,7 +4380,9 @@ int tz_net_init_random(tz_net* net, uint64_t seed) {
         init_const(st, "min", 1, 0.f);
         init_const(st, "max", 1, 1.f);
     }
-    if (net->has_hash) {
+    if (net->arch == TZ_ARCH_NET4_LCGHASH) {   // root.uniform("lcghash_init", [C, N, N], -100, 100), net4_lcghash.rs:131-136
+        init_uniform(st, seed, "lcghash_init", {cin, (uint32_t)net->n, (uint32_t)net->n}, -100.0, 100.0);
+    } else if (net->has_hash) {
         HostTensor t;
         t.dims = {cin * nn, 32};
         t.data.resize((size_t)cin * nn * 32);
@@ -4744,7 +4832,7 @@ int tz_net_hash_indices(tz_net* net, int batch, const tz_state* states, uint32_t
     hipError_t e = hipMalloc(&didx, batch * 4);
     if (e == hipSuccess) {
         rc = tz_net_ensure_batch(net, batch);
-        if (!rc) rc = launch_simhash_state(net->n, dstates, nullptr, net->simhash, net->bitset, nullptr, batch, batch, net->aux, didx, st);
+        if (!rc) rc = launch_hash_state(net, dstates, nullptr, nullptr, batch, batch, didx, st);
         if (!rc) {
             if (update) bitset_set_kernel<<<(batch + 255) / 256, 256, 0, st>>>(net->bitset, didx, batch);
             if (indices_out) e = hipMemcpyAsync(indices_out, didx, batch * 4, hipMemcpyDeviceToHost, st);
@@ -4755,6 +4843,35 @@ int tz_net_hash_indices(tz_net* net, int batch, const tz_state* states, uint32_t
     if (didx) (void)hipFree(didx);
     if (rc) return rc;
     if (e != hipSuccess) return tz_fail(TZ_EDEVICE, std::string("tz_net_hash_indices: ") + hipGetErrorString(e));
+    return TZ_OK;
+}
+
+// Diagnostic: the hash net's index-plus-lookup kernel alone, timed between two events (tools/lcghash_rate.py)
+int tz_debug_hash_bench(tz_net* net, int batch, const tz_state* states, int iters, float* ms_out) {
+    if (!net || !states || !ms_out || batch <= 0 || iters <= 0) return tz_fail(TZ_EINVAL, "tz_debug_hash_bench: bad argument");
+    if (!net->has_hash || !net->loaded) return tz_fail(TZ_ESTATE, "tz_debug_hash_bench: not a loaded SimHash network");
+    tz_state* dstates = nullptr;
+    int rc = net_upload_states(net, batch, states, &dstates);
+    if (rc) return rc;
+    hipStream_t st = net->stream;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    float ms = 0.f;
+    hipError_t e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    if (e == hipSuccess) rc = tz_net_ensure_batch(net, batch);
+    for (int i = 0; i < 2 && e == hipSuccess && !rc; i++) rc = launch_hash_state(net, dstates, nullptr, nullptr, batch, batch, nullptr, st);
+    if (e == hipSuccess && !rc) e = hipEventRecord(e0, st);
+    for (int i = 0; i < iters && e == hipSuccess && !rc; i++) rc = launch_hash_state(net, dstates, nullptr, nullptr, batch, batch, nullptr, st);
+    if (e == hipSuccess && !rc) e = hipEventRecord(e1, st);
+    if (e == hipSuccess && !rc) e = hipEventSynchronize(e1);
+    if (e == hipSuccess && !rc) e = hipEventElapsedTime(&ms, e0, e1);
+    if (e == hipSuccess && !rc) e = hipGetLastError();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    (void)hipFree(dstates);
+    if (rc) return rc;
+    if (e != hipSuccess) return tz_fail(TZ_EDEVICE, std::string("tz_debug_hash_bench: ") + hipGetErrorString(e));
+    *ms_out = ms / iters;
     return TZ_OK;
 }
 

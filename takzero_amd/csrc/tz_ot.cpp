@@ -677,7 +677,7 @@ void ot_tch_names(const TensorStore& in, NamedTensors& out) {
                           "rnd_learning.hidden_linear.bias", "rnd_learning.final_linear.weight", "rnd_learning.final_linear.bias",
                           "rnd_target.input_linear.weight", "rnd_target.input_linear.bias", "rnd_target.hidden_linear.weight",
                           "rnd_target.hidden_linear.bias", "rnd_target.final_linear.weight", "rnd_target.final_linear.bias", "min", "max",
-                          "simhash_matrix"};
+                          "simhash_matrix", "lcghash_init"};
     std::map<std::string, bool> done;
     for (auto& kv : out) done[kv.first] = true;
     for (const char* r : rest) {

@@ -88,7 +88,7 @@ class Trainer:
 
     def load_tensors(self, tensors):
         """VarStore contents by name (takzero_amd.weights / takzero_amd.ot).  The tensors the step never touches (RND nets,
-        SimHash matrix) go to the library with the rest, so save / to_net / the native save points carry them."""
+        SimHash matrix, lcghash_init) go to the library with the rest, so save / to_net / the native save points carry them."""
         from .weights import dumps_tzw
 
         missing = [k for k in self.names if k not in tensors]
@@ -169,7 +169,7 @@ class Trainer:
         return float(mn.value), float(mx.value)
 
     def extras(self):
-        """The variables the step never touches (RND nets, SimHash matrix), as the library carries them."""
+        """The variables the step never touches (RND nets, SimHash matrix, lcghash_init), as the library carries them."""
         from .weights import loads_tzw
 
         size = C.c_uint64()

@@ -70,7 +70,7 @@ def load_ot_libtorch(path):
 
 def tch_names(tensors):
     """The inverse (what tch would name the variables when it builds the net: creation order of net5.rs /
-    net6_simhash.rs, duplicates suffixed with the number of variables registered so far).  Used to write test
+    net6_simhash.rs / net4_lcghash.rs, duplicates suffixed with the number of variables registered so far).  Used to write test
     archives; the reader above does not depend on the exact numbers."""
     out, count = [], 0
     seen = set()

@@ -11,7 +11,7 @@ reference creates under one path, residual.rs:50-55) are spelled `.a.` and `.b.`
     u16 name length, name (utf-8), u8 ndim, u32 dims[ndim], f32 data (little endian, C order)
 
 Architectures: net5 (takzero/src/network/net5.rs:44-148), net4_simhash /
-net6_simhash (net6_simhash.rs:43-141).  `init_weights` follows tch's defaults as the reference
+net6_simhash (net6_simhash.rs:43-141), net4_lcghash (net4_lcghash.rs:39-140).  `init_weights` follows tch's defaults as the reference
 relies on them: conv/linear weights Kaiming-uniform(a=sqrt 5), biases U(+-1/sqrt(fan_in)),
 BatchNorm weight U(0,1), bias 0, running stats 0/1, RND min 0 / max 1 (net5.rs:166-168).
 """
@@ -22,6 +22,7 @@ import numpy as np
 ARCH_NET4_SIMHASH = 4
 ARCH_NET5 = 5
 ARCH_NET6_SIMHASH = 6
+ARCH_NET4_LCGHASH = 14
 ARCH_TEST = 100
 FILTERS = 256
 HASH_BITS = 32
@@ -38,11 +39,11 @@ def output_channels(n):
 
 
 def arch_blocks(arch, blocks=0):
-    return {ARCH_NET5: 20, ARCH_NET4_SIMHASH: 16, ARCH_NET6_SIMHASH: 16}.get(arch, blocks)
+    return {ARCH_NET5: 20, ARCH_NET4_SIMHASH: 16, ARCH_NET6_SIMHASH: 16, ARCH_NET4_LCGHASH: 16}.get(arch, blocks)
 
 
 def arch_board(arch, n=0):
-    return {ARCH_NET5: 5, ARCH_NET4_SIMHASH: 4, ARCH_NET6_SIMHASH: 6}.get(arch, n)
+    return {ARCH_NET5: 5, ARCH_NET4_SIMHASH: 4, ARCH_NET6_SIMHASH: 6, ARCH_NET4_LCGHASH: 4}.get(arch, n)
 
 
 def save_tzw(path, tensors):
@@ -144,6 +145,11 @@ def init_weights(arch, n=0, blocks=0, seed=123, trained_stats=False):
     if arch in (ARCH_NET4_SIMHASH, ARCH_NET6_SIMHASH):
         # simhash_matrix: root.var("simhash_matrix", [in_size, 32], Init::Randn{0,1}) net6_simhash.rs:133-137
         t["simhash_matrix"] = rng.normal(0.0, 1.0, size=(cin * nn, HASH_BITS)).astype(np.float32)
+    if arch == ARCH_NET4_LCGHASH:
+        # lcghash_init: root.uniform("lcghash_init", [channels, N, N], -100, 100) net4_lcghash.rs:131-136 (np.nextafter keeps the
+        # fp32 rounding of a draw just under 100 inside the half-open range)
+        u = rng.uniform(-100.0, 100.0, size=(cin, n, n)).astype(np.float32)
+        t["lcghash_init"] = np.minimum(u, np.nextafter(np.float32(100.0), np.float32(0.0)))
     return t
 
 
