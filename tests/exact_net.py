@@ -23,6 +23,10 @@ The first conv has zero weight on the five scalar input planes that are not dyad
 such as 17/21, flat difference / n^2): each precision stores those differently.  Those planes stay with the dense-weight tests
 (tests/test_gpu_net.py and the dense half of tests/test_gpu_net_forms.py); the colour-to-move plane (0 or 1) is used.
 
+`exact_weights_with_lo` gives the same nets a small lo part on every non-zero 3x3 weight, so that the correction products of the split
+arithmetics decide output bits; those nets are compared with the CPU emulation of tests/split_emulation.py
+(tests/test_split_emulation_reference.py holds nets and emulation to their conditions, tests/test_gpu_split_corrections.py runs them).
+
 `distinct_positions` returns positions that are all different (by their bytes): the opening position, a full board, on 6x6 the
 three wide positions of tests/test_gpu_edges.py, then every ply of random playouts."""
 import ctypes as C
@@ -108,10 +112,10 @@ def _sparse_conv(rng, cout, cin, allowed, p=None, second=None):
     return w
 
 
-def _calibrate_bias(pre):
+def _calibrate_bias(pre, ceiling=MAX_CALIBRATED):
     """pre [B,C,N,N] (integers, fp64): per channel the non-positive integer bias -k for which the share of outputs above zero is
     closest to SURVIVE, at least MIN_SHARE where a k >= 0 allows it (a positive bias only for a channel whose outputs are all <= 0), and
-    the largest output at most MAX_CALIBRATED."""
+    the largest output at most `ceiling`."""
     c = pre.shape[1]
     flat = np.rint(pre.transpose(1, 0, 2, 3).reshape(c, -1)).astype(np.int64)
     bias = np.zeros(c, np.float32)
@@ -125,7 +129,7 @@ def _calibrate_bias(pre):
                 k -= 1
         else:
             k = top - 1
-        bias[ch] = -max(k, top - MAX_CALIBRATED)
+        bias[ch] = -max(k, top - ceiling)
     return bias
 
 
@@ -146,8 +150,9 @@ def unfed_taps(weight, x):
     return out
 
 
-def exact_weights(arch, n, blocks, seed, calibration):
-    """Weights of `arch` as described in the module docstring; `calibration` are planes [B,C,N,N] (fp32) of encoded positions."""
+def exact_weights(arch, n, blocks, seed, calibration, ceiling=MAX_CALIBRATED):
+    """Weights of `arch` as described in the module docstring; `calibration` are planes [B,C,N,N] (fp32) of encoded positions;
+    `ceiling` is the largest activation the calibration allows on them."""
     import torch
     import torch.nn.functional as F
     from takzero_amd import weights as W
@@ -171,7 +176,7 @@ def exact_weights(arch, n, blocks, seed, calibration):
             pre = F.conv2d(x, t64(wt), padding=1)
             if residual is not None:
                 pre = pre + residual
-            b = _calibrate_bias(pre.numpy())
+            b = _calibrate_bias(pre.numpy(), ceiling)
             y = F.relu(pre + t64(b).view(1, -1, 1, 1))
             weak = np.flatnonzero((y != 0).double().mean(dim=(0, 2, 3)).numpy() < MIN_SHARE)
             if weak.size == 0:
@@ -209,6 +214,34 @@ def exact_weights(arch, n, blocks, seed, calibration):
         w[head + ".conv2d.bias"] = np.array([hb], np.float32)
         w[head + ".linear.weight"] = (sign * 2.0 ** -s).astype(np.float32).reshape(1, nn)
         w[head + ".linear.bias"] = np.array([0.25], np.float32)
+    return w
+
+
+LO_STEP = 2.0 ** -14      # exact_weights_with_lo: a weight is +-(1 + q * LO_STEP)
+LO_QMAX = 7
+LO_QMIN = 4               # q >= -4: 1 - 5 * 2^-14 and below round to the half 1 - 2^-11, and the hi parts would no longer be +-1 (-4 is a tie, to even)
+LO_NETS = {5: (100, 5, 3), 6: (100, 6, 2), 3: (100, 3, 2), 4: (100, 4, 2)}      # board size -> (arch, n, blocks): the test architecture
+LO_SEEDS = (0, 1)
+LO_ARITHMETICS = {5: ("f16x2", "f16c8", "f16c6"), 6: ("f16x2", "f16c8", "f16c6"), 3: ("f16x2", "f16c8"), 4: ("f16x2", "f16c8")}
+LO_POSITIONS, LO_POSITION_SEED, LO_CALIBRATION_SEED = 64, 77, 5
+LO_MIN_SHARE = 0.05
+LO_MIN_DECIDED = 0.5      # share of the policy outputs that the exactness condition covers, at least
+CONV_3X3 = lambda name, v: name.endswith("conv2d.weight") and v.shape[-1] == 3
+
+
+def exact_weights_with_lo(arch, n, blocks, seed, calibration, qmax=LO_QMAX, ceiling=MAX_CALIBRATED):
+    """`exact_weights` with a lo part on every non-zero weight of the first conv, the tower convs and the policy conv:
+    w = +-(1 + q * 2^-14), q a random integer in [-min(qmax, 4), qmax].  fp16(w) is still +-1, and the lo part q * 2^-14 is exact in fp16
+    (times 2^11), in E4M3 (times 2^11 and the layer's power of two) and in a block-scaled E2M3 code (integers up to 7 in units of
+    the block scale).  Structure, BatchNorms and the calibrated integer biases are those of the integer net; the heads keep their
+    dyadic weights.  With qmax = 0 the weights are `exact_weights` unchanged.  Activations are then integers plus a small lo part
+    (and a few tiny ones where the integers cancel), so the correction products of the split arithmetics decide output bits;
+    what has to hold for a bit-exact comparison is asserted by `assert_reference_is_exact` on the emulation's statistics."""
+    w = exact_weights(arch, n, blocks, seed, calibration, ceiling)
+    rng = np.random.default_rng(9000 + seed)
+    for name in sorted(k for k, v in w.items() if CONV_3X3(k, v)):
+        q = rng.integers(-min(qmax, LO_QMIN), qmax + 1, size=w[name].shape).astype(np.float64)
+        w[name] = (w[name].astype(np.float64) * (1.0 + q * LO_STEP)).astype(np.float32)
     return w
 
 
@@ -265,5 +298,21 @@ def exact_reference(w, planes, blocks, chunk=512):
 def assert_reference_is_exact(ref):
     """The conditions under which the bits of every precision must agree, on the positions a test runs (not only the calibration's)."""
     st = ref["stats"]
+    if "quotient" in st:
+        # A net with lo parts, emulated by tests/split_emulation.py.  The condition for a bit-exact comparison is not that values are
+        # integers but that no fp32 accumulator can round, in whatever order it adds: sum |terms| / (a power of two that divides
+        # every term) below 2^24, per output, for every accumulator of every layer.  Roundings then remain only at single,
+        # order-free operations (storage conversions and the one fp32 addition that merges the accumulators), which the emulation
+        # performs as the kernels do.  Activations near zero keep second-order bits (lo x lo sized, 2^-28) alive in their hi parts,
+        # and a block input carries 22 or more bits into the main accumulator, so the condition does not hold for every output of
+        # a net with a residual block, whatever the range of q, the calibration ceiling or the depth
+        # (tests/test_split_emulation_reference.py `test_the_levers_of_the_generator_do_not_make_the_condition_hold_everywhere`).  It is therefore applied per output: `decided` marks the outputs for which
+        # it holds in every accumulator they depend on, through every layer; those are compared bit for bit, and they must be
+        # most of the policy, on the positions a test runs.  No floor is set for the heads: they add 16 channels on every square, and
+        # few of their outputs (on some nets none) are decided.
+        dec = ref["decided"]
+        assert dec["policy"].mean() >= LO_MIN_DECIDED, dec["policy"].mean()
+        assert dec["policy"].any(axis=1).all()                # some decided logit in every position
+        return
     assert st["deviation"] < 1e-3, st
     assert st["max_activation"] <= MAX_ACTIVATION, st

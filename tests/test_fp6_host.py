@@ -10,37 +10,9 @@ import subprocess
 import numpy as np
 import pytest
 
+from e2m3_ref import e2m3_values, ref_code      # the numpy statement of the format, shared with tests/split_emulation.py
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def e2m3_values():
-    v = []
-    for c in range(32):
-        e, m = c >> 3, c & 7
-        v.append(m / 8.0 if e == 0 else (1.0 + m / 8.0) * 2.0 ** (e - 1))
-    return np.array(v, np.float64)   # ascending: 0 .. 7.5
-
-
-def ref_code(x):
-    """round to nearest even onto the grid, saturating; ties between codes c and c + 1 go to the even code"""
-    vals = e2m3_values()
-    a = abs(float(x))
-    if a != a:
-        c = 31
-    elif a >= 7.75:
-        c = 31
-    else:
-        i = int(np.searchsorted(vals, a, side="right")) - 1
-        i = max(0, min(30, i))
-        lo, hi = vals[i], vals[i + 1]
-        if a - lo < hi - a:
-            c = i
-        elif a - lo > hi - a:
-            c = i + 1
-        else:
-            c = i if i % 2 == 0 else i + 1
-    sign = 32 if np.signbit(np.float32(x)) else 0
-    return sign | c
 
 
 @pytest.fixture(scope="module")
