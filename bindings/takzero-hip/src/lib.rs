@@ -75,6 +75,14 @@ impl HipNet {
     pub fn raw(&self) -> *mut sys::TzNet {
         self.raw
     }
+    /// `EnsembleNetwork::forward_core_and_ensemble(xs, false)` (net4_ensemble.rs:157-171): the sixteen head values of every position.
+    /// `Err` unless the handle is a `sys::TZ_ARCH_NET4_ENSEMBLE` network.
+    pub fn ensemble_values(&self, envs: &[Env]) -> Result<Vec<[f32; sys::TZ_ENSEMBLE_SIZE as usize]>, TchError> {
+        let states: Vec<sys::TzState> = envs.iter().map(pack_state).collect();
+        let mut out = vec![[0.0f32; sys::TZ_ENSEMBLE_SIZE as usize]; states.len()];
+        check(unsafe { sys::tz_net_ensemble_values(self.raw, states.len() as i32, states.as_ptr(), out.as_mut_ptr() as *mut f32) })?;
+        Ok(out)
+    }
 }
 
 impl Drop for HipNet {

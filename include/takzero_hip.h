@@ -89,13 +89,17 @@ typedef struct tz_state {
 typedef struct tz_net tz_net;       /* opaque: a network on one GPU  (Network + Agent impl)   */
 typedef struct tz_search tz_search; /* opaque: BatchedMCTS<B, Game<N,HALF_KOMI>> on one GPU   */
 
-/* architectures (takzero/src/network/{net4_simhash,net5,net6_simhash,net4_lcghash}.rs) */
+/* architectures (takzero/src/network/{net4_simhash,net5,net6_simhash,net4_lcghash,net4_ensemble}.rs) */
 #define TZ_ARCH_NET4_SIMHASH 4
 #define TZ_ARCH_NET5 5
 #define TZ_ARCH_NET6_SIMHASH 6
 /* the trunk, heads and 2^32-bit set of net4_simhash; the set's index is an integer hash of planes * lcghash_init
  * (net4_lcghash.rs:202-242).  4x4 only.  Everything said about SimHash nets below holds for it. */
 #define TZ_ARCH_NET4_LCGHASH 14
+/* the trunk and heads of net4_simhash plus sixteen more value heads (`ensemble head i.*`); the local uncertainty is the population
+ * variance of their values (net4_ensemble.rs:146-171, 225-233).  4x4 only; no set of seen positions, no RND. */
+#define TZ_ARCH_NET4_ENSEMBLE 24
+#define TZ_ENSEMBLE_SIZE 16
 /* test architecture: same graph as net5 on any board size with configurable depth, no RND/hash */
 #define TZ_ARCH_TEST 100
 
@@ -193,6 +197,10 @@ int tz_net_encode(tz_net* net, int batch, const tz_state* states, float* planes_
 /* Full policy tensor [batch][policy_size] in the reference's NCHW flattening (net5.rs:238). */
 int tz_net_forward_raw(tz_net* net, int batch, const tz_state* states, float* policy_out,
                        float* value_out, float* ube_out);
+
+/* EnsembleNetwork::forward_core_and_ensemble(xs, false) (net4_ensemble.rs:157-171): the sixteen head values of every position,
+ * out[batch][16].  TZ_EINVAL unless the net is TZ_ARCH_NET4_ENSEMBLE. */
+int tz_net_ensemble_values(tz_net* net, int batch, const tz_state* states, float* out);
 
 /* Hash nets (net4_simhash / net6_simhash / net4_lcghash): HashNetwork::get_indices / update_counts
  * (net6_simhash.rs:202-243, net4_lcghash.rs:202-249) and the bitvec.bin file that accompanies a model (net6_simhash.rs:152-190). */
@@ -453,6 +461,18 @@ int tz_trainer_get_extras(tz_trainer* t, void* out, uint64_t cap, uint64_t* byte
 /* the variables of a network (tz_net_init_random = Net::new, or a loaded model) become the trainer's, and back */
 int tz_trainer_from_net(tz_trainer* t, tz_net* net);
 int tz_trainer_to_net(tz_trainer* t, tz_net* net);
+
+/* ---------- Training net4_ensemble's sixteen heads in the step (eee/src/ensemble.rs:318-351) ----------
+ * targets[batch][16] (copied) arm the trainer: every later tz_trainer_step also runs the sixteen heads on the step's detached trunk
+ * output in training mode, adds loss_ensemble = mean over [batch][16] of (target - value)^2, takes its gradient through the heads'
+ * own variables only, and with apply_step runs Adam on them (a step count of their own).  NULL disarms.  While armed the 64
+ * `ensemble head i.*` names answer to tz_trainer_get_tensor / _set_tensor (what 0..3).  With it never armed a trainer of this
+ * architecture carries the heads through unchanged.  TZ_EINVAL unless TZ_ARCH_NET4_ENSEMBLE; TZ_ESTATE when the loaded variables
+ * hold no `ensemble head i.*`.  The three losses and every gradient of the step itself are the same bytes armed or not: the heads
+ * run after it, on its last activation. */
+int tz_trainer_set_ensemble_targets(tz_trainer* t, const float* targets);
+/* loss_ensemble and the heads' values [batch][16] of the last armed step (before its update); either may be NULL; TZ_ESTATE before one. */
+int tz_trainer_ensemble_last(tz_trainer* t, float* loss_out, float* values_out);
 
 /* ---------- Training net5's RND predictor in the step (net5.rs:193-218; learn/src/main.rs:404-405, 415-416) ----------
  * The reference ships loss_rnd = forward_rnd(input, true).mean() and update_rnd switched off by comments; here both are present

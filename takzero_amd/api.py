@@ -14,7 +14,8 @@ import numpy as np
 from . import _lib
 from ._lib import ROOT_INFO_DTYPE, STATE_DTYPE, TakzeroError, check
 
-ARCH_NET4_SIMHASH, ARCH_NET5, ARCH_NET6_SIMHASH, ARCH_NET4_LCGHASH, ARCH_TEST = 4, 5, 6, 14, 100
+ARCH_NET4_SIMHASH, ARCH_NET5, ARCH_NET6_SIMHASH, ARCH_NET4_LCGHASH, ARCH_NET4_ENSEMBLE, ARCH_TEST = 4, 5, 6, 14, 24, 100
+ENSEMBLE_SIZE = 16
 PREC_BF16, PREC_F32, PREC_F16, PREC_F16X2, PREC_F16C8, PREC_F16C6 = 0, 1, 2, 3, 4, 5
 # Arithmetic of the trunk.  fp16 storage with fp32 accumulation (PREC_F16) is the throughput default: its logits are within
 # ~2e-4 *relative* of the fp32 graph through the 41 stacked convs (1.5e-4 absolute at the random-init logit scale of 0.2,
@@ -105,7 +106,7 @@ class Net:
         check(self.lib.tz_net_create(n, arch, device, precision, blocks, C.byref(h)))
         self.h = h
         self.arch, self.precision, self.blocks, self.device = arch, precision, blocks, device
-        self.n = {ARCH_NET5: 5, ARCH_NET4_SIMHASH: 4, ARCH_NET6_SIMHASH: 6, ARCH_NET4_LCGHASH: 4}.get(arch, n)
+        self.n = {ARCH_NET5: 5, ARCH_NET4_SIMHASH: 4, ARCH_NET6_SIMHASH: 6, ARCH_NET4_LCGHASH: 4, ARCH_NET4_ENSEMBLE: 4}.get(arch, n)
 
     def close(self):
         if getattr(self, "h", None):
@@ -202,6 +203,13 @@ class Net:
         check(self.lib.tz_net_eval(self.h, b, st.ctypes.data, idx.ctypes.data, cnt.ctypes.data, amax,
                                    logits.ctypes.data, value.ctypes.data, var.ctypes.data))
         return [logits[i, :cnt[i]].copy() for i in range(b)], value, var
+
+    def ensemble_values(self, env_batch):
+        """EnsembleNetwork::forward_core_and_ensemble(xs, false), net4_ensemble.rs:157-171: the sixteen head values, [B, 16]."""
+        st = _states(env_batch)
+        out = np.zeros((len(st), ENSEMBLE_SIZE), np.float32)
+        check(self.lib.tz_net_ensemble_values(self.h, len(st), st.ctypes.data, out.ctypes.data))
+        return out
 
     def hash_indices(self, env_batch, update=False):
         """HashNetwork::get_indices (and update_counts when update=True), net6_simhash.rs:202-243 / net4_lcghash.rs:202-249."""

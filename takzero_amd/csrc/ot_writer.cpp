@@ -1,7 +1,7 @@
 // ot_writer — writes a LibTorch archive exactly as tch's VarStore::save does (network/mod.rs:16-18 -> torch-sys
 // at_save_multi: OutputArchive::write(name, tensor) for every variable, then save_to), so that the reference's
 // Net::load reads models trained here.  Host tool of takzero_amd.ot.save_ot; input: a text manifest of
-// "<archive name> <n dims> <dims...> <raw f32 file>" lines.  Built on demand with g++ against the torch wheel.
+// "<archive name><tab><n dims> <dims...> <raw f32 file>" lines (a name may hold spaces: `ensemble head 3.conv2d.weight`).  Built on demand with g++ against the torch wheel.
 #include <torch/torch.h>
 
 #include <fstream>
@@ -18,7 +18,8 @@ int main(int argc, char** argv) {
         std::istringstream ls(line);
         std::string name, file;
         int nd;
-        ls >> name >> nd;
+        std::getline(ls, name, '\t');
+        ls >> nd;
         std::vector<int64_t> dims(nd);
         int64_t total = 1;
         for (auto& d : dims) {

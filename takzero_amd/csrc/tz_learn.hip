@@ -713,7 +713,8 @@ __global__ void losses_kernel(const float* lp, const float* lv, const float* lu,
 
 // torch.optim.Adam (tch nn::Adam::default(): beta1 0.9, beta2 0.999, eps 1e-8, no weight decay, no amsgrad).
 // group[block of 1024 elements]: 0 = not trained, 1 = stepped every call, 2 = the UBE head (stepped when trained),
-// 3 = the RND predictor (its own arena and launch; counts its own steps, as torch's Adam does per parameter).
+// 3 = a side arena with a launch of its own, whose step count arrives as t_rnd: the RND predictor, or net4_ensemble's sixteen heads
+// (each counts its own steps, as torch's Adam does per parameter).
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ P, const float* __restrict__ G, float* __restrict__ M1,
                                                    float* __restrict__ M2, const uint8_t* __restrict__ group, float lr,
                                                    int t_main, int t_ube, int t_rnd) {
@@ -733,6 +734,93 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ P, const 
         M2[i] = v;
         P[i] -= step_size * (m / (sqrtf(v) / bc2_sqrt + eps));
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The sixteen heads of net4_ensemble on the step's detached trunk output (eee/src/ensemble.rs:318-351; net4_ensemble.rs:146-171):
+// value_i = tanh(Linear_i(relu(conv1x1_i(T) + b_i))), loss_ensemble = mean over [batch][16] of (target - value)^2, gradients of the
+// heads' own variables only.  One arena per kind (parameters, gradients, two moments): conv weights [head][256] at ENS_CW, conv
+// biases [16] at ENS_CB, linear weights [head][16 squares] at ENS_LW, linear biases [16] at ENS_LB, padded to whole Adam blocks.
+constexpr int ENS = TZ_ENSEMBLE_SIZE, ENS_NN = 16, ENS_CW = 0, ENS_CB = ENS * FILTERS, ENS_LW = ENS_CB + ENS, ENS_LB = ENS_LW + ENS * ENS_NN,
+              ENS_COUNT = ENS_LB + ENS, ENS_SLOTS = (ENS_COUNT + 1023) / 1024 * 1024;
+
+// forward of one board and what the backward needs of it: thread (square s, head h) takes the conv in channel order, thread h the
+// Linear in square order and tanh; then dz = 2 (v - t) / (16 B) * (1 - v^2) (the gradient at the Linear's output), the squared error,
+// and per (head, square) the conv output after ReLU and the gradient at the conv's output
+__global__ __launch_bounds__(256) void ens_fwd_kernel(const float* __restrict__ T, const float* __restrict__ P, const float* __restrict__ target,
+                                                      int batch, float* __restrict__ values, float* __restrict__ relu,
+                                                      float* __restrict__ dz, float* __restrict__ dconv, float* __restrict__ err2) {
+    __shared__ float pre[ENS][ENS_NN + 1];
+    __shared__ float dzs[ENS];
+    const int b = blockIdx.x, tid = threadIdx.x, h = tid & 15, s = tid >> 4;
+    const float* row = T + ((size_t)b * ENS_NN + s) * FILTERS;
+    const float* w = P + ENS_CW + h * FILTERS;
+    float acc = 0.f;
+    for (int c = 0; c < FILTERS; c++) acc += row[c] * w[c];
+    acc += P[ENS_CB + h];
+    const float r = fmaxf(acc, 0.f);
+    pre[h][s] = r;
+    relu[((size_t)b * ENS + h) * ENS_NN + s] = r;
+    __syncthreads();
+    if (tid < ENS) {
+        float lin = 0.f;
+        for (int px = 0; px < ENS_NN; px++) lin += pre[tid][px] * P[ENS_LW + tid * ENS_NN + px];
+        const float v = tanhf(lin + P[ENS_LB + tid]);
+        const float e = v - target[(size_t)b * ENS + tid];
+        const float d = 2.f * e / (float)(ENS * batch) * (1.f - v * v);
+        values[(size_t)b * ENS + tid] = v;
+        err2[(size_t)b * ENS + tid] = e * e;
+        dz[(size_t)b * ENS + tid] = d;
+        dzs[tid] = d;
+    }
+    __syncthreads();
+    dconv[((size_t)b * ENS + h) * ENS_NN + s] = r > 0.f ? dzs[h] * P[ENS_LW + h * ENS_NN + s] : 0.f;
+}
+
+// gradients of head h = blockIdx.x in two stages, every sum in double and in a fixed order.  Stage one, one workgroup per (head, chunk
+// of ENS_CHUNK boards): thread c the conv weight's gradient [256] over the chunk's 16 * ENS_CHUNK rows of T (boards in order, squares
+// inside a board in order); threads 0..15 the Linear weights', thread 16 the Linear bias's, thread 17 the conv bias's; thread 18 of
+// head 0 the chunk's squared errors.  Stage two, one workgroup per head, adds the chunks up in chunk order.
+constexpr int ENS_CHUNK = 8, ENS_SMALL = 32;
+__global__ __launch_bounds__(256) void ens_bwd_kernel(const float* __restrict__ T, const float* __restrict__ relu, const float* __restrict__ dz,
+                                                      const float* __restrict__ dconv, const float* __restrict__ err2,
+                                                      double* __restrict__ part, double* __restrict__ small) {
+    const int h = blockIdx.x, chunk = blockIdx.y, tid = threadIdx.x, b0 = chunk * ENS_CHUNK;
+    double g = 0.0;
+    for (int b = b0; b < b0 + ENS_CHUNK; b++)
+        for (int s = 0; s < ENS_NN; s++) {
+            const float d = dconv[((size_t)b * ENS + h) * ENS_NN + s];
+            if (d != 0.f) g += (double)d * (double)T[((size_t)b * ENS_NN + s) * FILTERS + tid];
+        }
+    part[((size_t)chunk * ENS + h) * FILTERS + tid] = g;
+    if (tid >= ENS_SMALL) return;
+    double a = 0.0;
+    if (tid < ENS_NN) {
+        for (int b = b0; b < b0 + ENS_CHUNK; b++) a += (double)dz[(size_t)b * ENS + h] * (double)relu[((size_t)b * ENS + h) * ENS_NN + tid];
+    } else if (tid == 16) {
+        for (int b = b0; b < b0 + ENS_CHUNK; b++) a += (double)dz[(size_t)b * ENS + h];
+    } else if (tid == 17) {
+        for (int b = b0; b < b0 + ENS_CHUNK; b++)
+            for (int s = 0; s < ENS_NN; s++) a += (double)dconv[((size_t)b * ENS + h) * ENS_NN + s];
+    } else if (tid == 18 && h == 0) {
+        for (int i = b0 * ENS; i < (b0 + ENS_CHUNK) * ENS; i++) a += (double)err2[i];
+    }
+    small[((size_t)chunk * ENS + h) * ENS_SMALL + tid] = a;
+}
+
+__global__ __launch_bounds__(256) void ens_bwd_finish_kernel(const double* __restrict__ part, const double* __restrict__ small, int batch,
+                                                             float* __restrict__ G, float* __restrict__ loss) {
+    const int h = blockIdx.x, tid = threadIdx.x, chunks = batch / ENS_CHUNK;
+    double g = 0.0;
+    for (int k = 0; k < chunks; k++) g += part[((size_t)k * ENS + h) * FILTERS + tid];
+    G[ENS_CW + h * FILTERS + tid] = (float)g;
+    if (tid > 18) return;
+    double a = 0.0;
+    for (int k = 0; k < chunks; k++) a += small[((size_t)k * ENS + h) * ENS_SMALL + tid];
+    if (tid < ENS_NN) G[ENS_LW + h * ENS_NN + tid] = (float)a;
+    else if (tid == 16) G[ENS_LB + h] = (float)a;
+    else if (tid == 17) G[ENS_CB + h] = (float)a;
+    else if (h == 0) loss[0] = (float)(a / (double)(batch * ENS));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -883,6 +971,18 @@ struct Rnd {
     bool have_last = false;
 };
 
+// The ensemble side of a net4_ensemble trainer, allocated when tz_trainer_set_ensemble_targets first arms it.  While armed the device
+// holds the current `ensemble head i.*`; ens_download brings them to the carried variables before anything reads those.
+struct Ens {
+    bool allocated = false, armed = false, have_last = false;
+    int t_ens = 0;
+    float *P = nullptr, *G = nullptr, *M1 = nullptr, *M2 = nullptr;
+    uint8_t* group = nullptr;
+    float *targets = nullptr, *values = nullptr, *relu = nullptr, *dz = nullptr, *dconv = nullptr, *err2 = nullptr, *loss = nullptr;
+    double *part = nullptr, *small = nullptr;   // ens_bwd_kernel's per-chunk sums
+    float last_loss = 0.f;
+};
+
 }  // namespace
 
 struct tz_trainer {
@@ -925,6 +1025,7 @@ struct tz_trainer {
     // training is enabled the device holds the current rnd_learning.*; rnd_download brings them here before anything reads them.
     TensorStore extra;
     Rnd rnd;
+    Ens ens;
 };
 
 namespace {
@@ -1347,6 +1448,92 @@ int rnd_allocate(tz_trainer* t) {
     return TZ_OK;
 }
 
+// place and size of an `ensemble head i.*` variable in the arena; false for any other name
+const char* const ENS_PARTS[4] = {".conv2d.weight", ".conv2d.bias", ".linear.weight", ".linear.bias"};
+std::string ens_name(int head, int part) { return "ensemble head " + std::to_string(head) + ENS_PARTS[part]; }
+void ens_place(int head, int part, size_t& off, size_t& count) {
+    count = part == 0 ? FILTERS : part == 2 ? ENS_NN : 1;
+    off = part == 0 ? ENS_CW + (size_t)head * FILTERS : part == 1 ? ENS_CB + head : part == 2 ? ENS_LW + (size_t)head * ENS_NN : ENS_LB + head;
+}
+bool ens_find(const std::string& name, size_t& off, size_t& count) {
+    for (int head = 0; head < ENS; head++)
+        for (int part = 0; part < 4; part++)
+            if (name == ens_name(head, part)) {
+                ens_place(head, part, off, count);
+                return true;
+            }
+    return false;
+}
+bool ens_variables_present(const tz_trainer* t) {
+    for (int head = 0; head < ENS; head++)
+        for (int part = 0; part < 4; part++) {
+            size_t off, count;
+            ens_place(head, part, off, count);
+            auto it = t->extra.find(ens_name(head, part));
+            if (it == t->extra.end() || it->second.data.size() != count) return false;
+        }
+    return true;
+}
+// the carried heads go to the device (parameters only: gradients and moments stay) ...
+int ens_upload(tz_trainer* t) {
+    std::vector<float> host(ENS_SLOTS, 0.f);
+    for (int head = 0; head < ENS; head++)
+        for (int part = 0; part < 4; part++) {
+            size_t off, count;
+            ens_place(head, part, off, count);
+            memcpy(host.data() + off, t->extra.at(ens_name(head, part)).data.data(), count * sizeof(float));
+        }
+    TZ_HIP(hipStreamSynchronize(t->stream));
+    TZ_HIP(hipMemcpy(t->ens.P, host.data(), ENS_SLOTS * sizeof(float), hipMemcpyHostToDevice));
+    return TZ_OK;
+}
+// ... and the current ones come back into the carried variables
+int ens_download(tz_trainer* t) {
+    std::vector<float> host(ENS_SLOTS);
+    TZ_HIP(hipSetDevice(t->device));
+    TZ_HIP(hipStreamSynchronize(t->stream));
+    TZ_HIP(hipMemcpy(host.data(), t->ens.P, ENS_SLOTS * sizeof(float), hipMemcpyDeviceToHost));
+    for (int head = 0; head < ENS; head++)
+        for (int part = 0; part < 4; part++) {
+            size_t off, count;
+            ens_place(head, part, off, count);
+            HostTensor& h = t->extra[ens_name(head, part)];
+            h.data.assign(host.begin() + off, host.begin() + off + count);
+        }
+    return TZ_OK;
+}
+int ens_allocate(tz_trainer* t) {
+    Ens& e = t->ens;
+    if (e.allocated) return TZ_OK;
+    const size_t B = (size_t)t->batch;
+    int rc;
+    if ((rc = dalloc(t, &e.P, (size_t)ENS_SLOTS)) || (rc = dalloc(t, &e.G, (size_t)ENS_SLOTS)) || (rc = dalloc(t, &e.M1, (size_t)ENS_SLOTS)) ||
+        (rc = dalloc(t, &e.M2, (size_t)ENS_SLOTS)) || (rc = dalloc(t, &e.group, (size_t)ENS_SLOTS / 1024)) || (rc = dalloc(t, &e.targets, B * ENS)) ||
+        (rc = dalloc(t, &e.values, B * ENS)) || (rc = dalloc(t, &e.relu, B * ENS * ENS_NN)) || (rc = dalloc(t, &e.dz, B * ENS)) ||
+        (rc = dalloc(t, &e.dconv, B * ENS * ENS_NN)) || (rc = dalloc(t, &e.err2, B * ENS)) || (rc = dalloc(t, &e.loss, (size_t)4)) ||
+        (rc = dalloc(t, &e.part, B / ENS_CHUNK * ENS * FILTERS)) || (rc = dalloc(t, &e.small, B / ENS_CHUNK * ENS * ENS_SMALL)))
+        return rc;
+    TZ_HIP(hipMemset(e.group, 3, ENS_SLOTS / 1024));   // adam_kernel's group of a side arena: the step count passed as t_rnd
+    e.allocated = true;
+    return TZ_OK;
+}
+// the armed part of a step, on the step's stream behind its backward: nothing of the step itself is reordered or reads what this writes
+int ens_chain(tz_trainer* t, int apply_step) {
+    Ens& e = t->ens;
+    const float* T = t->a[t->layers - 1];
+    ens_fwd_kernel<<<t->batch, 256, 0, t->stream>>>(T, e.P, e.targets, t->batch, e.values, e.relu, e.dz, e.dconv, e.err2);
+    ens_bwd_kernel<<<dim3(ENS, t->batch / ENS_CHUNK), 256, 0, t->stream>>>(T, e.relu, e.dz, e.dconv, e.err2, e.part, e.small);
+    ens_bwd_finish_kernel<<<ENS, 256, 0, t->stream>>>(e.part, e.small, t->batch, e.G, e.loss);
+    int rc;
+    if ((rc = launch_check("ensemble heads"))) return rc;
+    if (apply_step) {
+        e.t_ens++;
+        adam_kernel<<<ENS_SLOTS / 1024, 256, 0, t->stream>>>(e.P, e.G, e.M1, e.M2, e.group, t->lr, 0, 0, e.t_ens);
+        if ((rc = launch_check("ensemble adam"))) return rc;
+    }
+    return TZ_OK;
+}
+
 }  // namespace
 // ------------------------------------------------------------------------------------------------
 // C ABI (include/takzero_hip.h, "Trainer")
@@ -1360,6 +1547,7 @@ int tz_trainer_create(int board_n, int arch, int device_id, int blocks, int batc
     if (arch == TZ_ARCH_NET4_SIMHASH && board_n != 4) return tz_fail(TZ_EINVAL, "tz_trainer_create: net4_simhash is 4x4");
     if (arch == TZ_ARCH_NET6_SIMHASH && board_n != 6) return tz_fail(TZ_EINVAL, "tz_trainer_create: net6_simhash is 6x6");
     if (arch == TZ_ARCH_NET4_LCGHASH && board_n != 4) return tz_fail(TZ_EINVAL, "tz_trainer_create: net4_lcghash is 4x4");
+    if (arch == TZ_ARCH_NET4_ENSEMBLE && board_n != 4) return tz_fail(TZ_EINVAL, "tz_trainer_create: net4_ensemble is 4x4");
     if (batch <= 0 || batch % 64) return tz_fail(TZ_EINVAL, "tz_trainer_create: batch must be a positive multiple of 64");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev)
@@ -1547,6 +1735,17 @@ int tz_trainer_set_tensor(tz_trainer* t, const char* name, int what, const float
         TZ_HIP(hipMemcpy(ra + r.off[i], host.data(), r.slots[i] * sizeof(float), hipMemcpyHostToDevice));
         return TZ_OK;
     }
+    size_t eoff = 0, ecount = 0;
+    if (t->ens.armed && ens_find(name, eoff, ecount)) {   // the heads' variables answer while the trainer is armed
+        Ens& e = t->ens;
+        float* ea = what == 0 ? e.P : what == 1 ? e.G : what == 2 ? e.M1 : what == 3 ? e.M2 : nullptr;
+        if (!ea) return tz_fail(TZ_EINVAL, std::string("tz_trainer_set_tensor: unknown tensor ") + name);
+        if (count != ecount) return tz_fail(TZ_EPARSE, std::string("tz_trainer_set_tensor: wrong size for ") + name);
+        TZ_HIP(hipSetDevice(t->device));
+        TZ_HIP(hipStreamSynchronize(t->stream));
+        TZ_HIP(hipMemcpy(ea + eoff, data, ecount * sizeof(float), hipMemcpyHostToDevice));
+        return TZ_OK;
+    }
     auto it = t->index.find(name);
     float* arena = arena_of(t, what);
     if (it == t->index.end() || !arena) return tz_fail(TZ_EINVAL, std::string("tz_trainer_set_tensor: unknown tensor ") + name);
@@ -1581,6 +1780,17 @@ int tz_trainer_get_tensor(tz_trainer* t, const char* name, int what, float* out,
         TZ_HIP(hipStreamSynchronize(r.stream));
         TZ_HIP(hipMemcpy(host.data(), ra + r.off[i], r.slots[i] * sizeof(float), hipMemcpyDeviceToHost));
         rnd_unpack(i, host, out);
+        return TZ_OK;
+    }
+    size_t eoff = 0, ecount = 0;
+    if (t->ens.armed && ens_find(name, eoff, ecount)) {
+        const Ens& e = t->ens;
+        const float* ea = what == 0 ? e.P : what == 1 ? e.G : what == 2 ? e.M1 : what == 3 ? e.M2 : nullptr;
+        if (!ea) return tz_fail(TZ_EINVAL, std::string("tz_trainer_get_tensor: unknown tensor ") + name);
+        if (count != ecount) return tz_fail(TZ_EPARSE, std::string("tz_trainer_get_tensor: wrong size for ") + name);
+        TZ_HIP(hipSetDevice(t->device));
+        TZ_HIP(hipStreamSynchronize(t->stream));
+        TZ_HIP(hipMemcpy(out, ea + eoff, ecount * sizeof(float), hipMemcpyDeviceToHost));
         return TZ_OK;
     }
     auto it = t->index.find(name);
@@ -1618,6 +1828,10 @@ int tz_trainer_snapshot(tz_trainer* t, TensorStore& out) {
         int rc = rnd_download(t);
         if (rc) return rc;
     }
+    if (t->ens.armed) {
+        int rc = ens_download(t);
+        if (rc) return rc;
+    }
     out = t->extra;
     for (const Param& p : t->params) {
         HostTensor h;
@@ -1643,6 +1857,14 @@ static int trainer_apply_store(tz_trainer* t, const TensorStore& st) {
     t->extra.clear();
     for (auto& kv : st)
         if (!t->index.count(kv.first)) t->extra[kv.first] = kv.second;
+    if (t->ens.armed) {   // the loaded model's heads replace the device's (moments stay, as for the other parameters)
+        if (!ens_variables_present(t)) {
+            t->ens.armed = false;
+            return tz_fail(TZ_ESTATE, "trainer: the loaded model holds no ensemble heads; the trainer is disarmed");
+        }
+        int rc = ens_upload(t);
+        if (rc) return rc;
+    }
     if (t->rnd.on) {   // the loaded model's RND nets replace the device's (moments stay, as for the other parameters)
         if (!rnd_variables_present(t)) {
             t->rnd.on = false;
@@ -1676,6 +1898,10 @@ int tz_trainer_get_extras(tz_trainer* t, void* out, uint64_t cap, uint64_t* byte
     if (!t) return tz_fail(TZ_EINVAL, "tz_trainer_get_extras: null handle");
     if (t->rnd.on) {
         int rc = rnd_download(t);
+        if (rc) return rc;
+    }
+    if (t->ens.armed) {
+        int rc = ens_download(t);
         if (rc) return rc;
     }
     std::vector<unsigned char> blob;
@@ -1733,6 +1959,7 @@ int tz_trainer_step(tz_trainer* t, const tz_state* states, const float* target_p
     if (t->rnd.on && (rc = rnd_chain(t, apply_step))) return rc;
     if ((rc = backward(t, train_ube))) return rc;
     if (t->rnd.on) TZ_HIP(hipStreamWaitEvent(t->stream, t->rnd.ev_done, 0));
+    if (t->ens.armed && (rc = ens_chain(t, apply_step))) return rc;
     if (apply_step) {
         t->t_main++;
         if (train_ube) t->t_ube++;
@@ -1740,18 +1967,24 @@ int tz_trainer_step(tz_trainer* t, const tz_state* states, const float* target_p
                                                                         t->t_main, train_ube ? t->t_ube : 0, 0);
         if ((rc = launch_check("adam"))) return rc;
     }
-    float losses[4] = {0, 0, 0, 0};
+    float losses[4] = {0, 0, 0, 0}, loss_ens = 0.f;
     TZ_HIP(hipMemcpyAsync(losses, t->losses, sizeof(float) * 3, hipMemcpyDeviceToHost, t->stream));
+    if (t->ens.armed) TZ_HIP(hipMemcpyAsync(&loss_ens, t->ens.loss, sizeof(float), hipMemcpyDeviceToHost, t->stream));
     if (t->rnd.on) TZ_HIP(hipMemcpyAsync(&losses[3], t->rnd.loss, sizeof(float), hipMemcpyDeviceToHost, t->stream));
     TZ_HIP(hipStreamSynchronize(t->stream));
     if (t->rnd.on) {
         t->rnd.last_loss = losses[3];
         t->rnd.have_last = true;
     }
+    if (t->ens.armed) {
+        t->ens.last_loss = loss_ens;
+        t->ens.have_last = true;
+    }
     if (losses_out) memcpy(losses_out, losses, sizeof(float) * 3);
     if (!(losses[0] == losses[0]) || !(losses[1] == losses[1]) || !(losses[2] == losses[2]))
         return tz_fail(TZ_ENUMERIC, "tz_trainer_step: a loss is NaN");
     if (t->rnd.on && !(losses[3] == losses[3])) return tz_fail(TZ_ENUMERIC, "tz_trainer_step: loss_rnd is NaN");
+    if (t->ens.armed && !(loss_ens == loss_ens)) return tz_fail(TZ_ENUMERIC, "tz_trainer_step: loss_ensemble is NaN");
     return TZ_OK;
 }
 
@@ -1782,6 +2015,38 @@ int tz_trainer_activation(tz_trainer* t, int layer, float* out, uint64_t cap) {
     TZ_HIP(hipSetDevice(t->device));
     TZ_HIP(hipStreamSynchronize(t->stream));
     TZ_HIP(hipMemcpy(out, t->a[layer], real * sizeof(float), hipMemcpyDeviceToHost));
+    return TZ_OK;
+}
+
+// ---- training net4_ensemble's heads (eee/src/ensemble.rs:318-351) ----
+int tz_trainer_set_ensemble_targets(tz_trainer* t, const float* targets) {
+    if (!t) return tz_fail(TZ_EINVAL, "tz_trainer_set_ensemble_targets: null handle");
+    if (t->arch != TZ_ARCH_NET4_ENSEMBLE) return tz_fail(TZ_EINVAL, "tz_trainer_set_ensemble_targets: only net4_ensemble has ensemble heads");
+    TZ_HIP(hipSetDevice(t->device));
+    int rc;
+    if (!targets) {
+        if (t->ens.armed && (rc = ens_download(t))) return rc;   // the trained heads stay with the carried variables
+        t->ens.armed = false;
+        return TZ_OK;
+    }
+    if (!t->ens.armed) {
+        if (!ens_variables_present(t)) return tz_fail(TZ_ESTATE, "tz_trainer_set_ensemble_targets: the loaded variables hold no `ensemble head i.*`");
+        if ((rc = ens_allocate(t))) return rc;
+        if ((rc = ens_upload(t))) return rc;
+        t->ens.armed = true;
+    }
+    TZ_HIP(hipStreamSynchronize(t->stream));
+    TZ_HIP(hipMemcpy(t->ens.targets, targets, sizeof(float) * t->batch * ENS, hipMemcpyHostToDevice));
+    return TZ_OK;
+}
+
+int tz_trainer_ensemble_last(tz_trainer* t, float* loss_out, float* values_out) {
+    if (!t) return tz_fail(TZ_EINVAL, "tz_trainer_ensemble_last: null handle");
+    if (!t->ens.allocated || !t->ens.have_last) return tz_fail(TZ_ESTATE, "tz_trainer_ensemble_last: no armed step yet");
+    TZ_HIP(hipSetDevice(t->device));
+    TZ_HIP(hipStreamSynchronize(t->stream));
+    if (loss_out) *loss_out = t->ens.last_loss;
+    if (values_out) TZ_HIP(hipMemcpy(values_out, t->ens.values, sizeof(float) * t->batch * ENS, hipMemcpyDeviceToHost));
     return TZ_OK;
 }
 

@@ -20,7 +20,7 @@ struct ConvW {
 struct tz_net {
     int n = 0, nn = 0, arch = 0, device = 0, precision = 0, blocks = 0;
     int cin = 0, cin_pad = 0, pol_ch = 0, pol_stride = 0, ppt = 0;
-    bool loaded = false, has_rnd = false, has_hash = false;
+    bool loaded = false, has_rnd = false, has_hash = false, has_ens = false;
     TensorStore store;         // host copy of the VarStore (fp32, `.a.` / `.b.` names): tz_net_save / clone / load_partial
     uint64_t capture_gen = 0;  // tz_net_invalidate_captures: bumped whenever something a captured simulation names is replaced
     ConvW conv_in, policy;
@@ -37,6 +37,7 @@ struct tz_net {
     float rnd_min = 0.0f, rnd_max = 1.0f;
     float* simhash = nullptr;    // [in_size][32] fp32, reference order (c*nn + px); TZ_ARCH_NET4_LCGHASH: lcghash_init, [in_size] in that order
     uint32_t* bitset = nullptr;  // 2^32 bits, allocated for hash archs
+    float* ens_w = nullptr;      // TZ_ARCH_NET4_ENSEMBLE: [conv w [256][16], linear w [16][nn], conv bias [16], linear bias [16]] (ensemble_heads_kernel)
     // work buffers, sized for max_batch positions
     int max_batch = 0;
     void *act_a = nullptr, *act_b = nullptr, *act_c = nullptr;  // [max_batch*nn][256] bf16 or f32
@@ -45,6 +46,8 @@ struct tz_net {
     float *value = nullptr, *ube = nullptr, *variance = nullptr, *aux = nullptr;  // [max_batch]
     void *rnd_in = nullptr, *rnd_h1 = nullptr, *rnd_h2 = nullptr;  // RND activations
     float* rnd_out = nullptr;                                       // [2][max_batch][512]
+    float* ens_act = nullptr;     // TZ_ARCH_NET4_ENSEMBLE: the tower's last image as the fused launch stores it, [max_batch*nn][256] fp32
+    float* ens_values = nullptr;  //   ... and the sixteen head values, [max_batch][16]
     void* seeds = nullptr;     // TZ_PREC_F16C6: the blocks' inputs (fp32) between the two convs of a block (tz_nn_c6.hip)
     // tz_net_eval at small batches: several CUs per board group (net_mfma_kernel SPLIT): the groups' exchange buffer and arrival
     // counters, allocated at the first such call; `eval_split` is set for the duration of a tz_net_eval call only

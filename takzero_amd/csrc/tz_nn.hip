@@ -17,6 +17,7 @@
 #include "tz_nn.h"
 #include "tz_fp8.h"
 #include "tz_fp6.h"
+#include "tz_math.h"
 #include <type_traits>
 #include "tz_ot.h"
 
@@ -947,6 +948,8 @@ struct NetArgs {
     // their arrival counters (one 128-byte line each, zeroed before the launch)
     unsigned char* xch;
     unsigned* xch_count;
+    // ENS (TZ_ARCH_NET4_ENSEMBLE): the tower's last image leaves for the ensemble heads' kernel, [position * nn + square][256] fp32
+    float* ens_act;
 };
 
 // 72 k-steps of one 256-input-channel 3x3 conv out of the LDS image: activation fragments one k-step ahead,
@@ -1870,10 +1873,11 @@ __device__ __forceinline__ void split_halves(float v, _Float16& hi, _Float16& lo
 // b + 16, b + 24: one XCD under the dispatcher's round-robin, where the exchange is fastest (the L2 serves it), but nothing depends
 // on that.  A member that waits seconds for its partners poisons its outputs with NaN instead of hanging.  The accumulation order of
 // an output does not depend on SPLIT (same k-loop, other RN): same bits as every other form.
-template <int NB, int P, int RNP, typename ET, bool PERM = false, int SP = 0, int ABL = 0, int TT = 0, int NW = 8, int SPLIT = 1>
+template <int NB, int P, int RNP, typename ET, bool PERM = false, int SP = 0, int ABL = 0, int TT = 0, int NW = 8, int SPLIT = 1, bool ENS = false>
 __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void net_mfma_kernel(NetArgs a) {
     typedef typename Elem<ET>::x8 ex8;
     typedef typename Elem<ET>::x4 ex4;
+    static_assert(!ENS || (NB == 4 && !PERM && SPLIT == 1), "the ensemble net's store: the one-CU 4x4 forms, board-major rows");
     static_assert(!SP || sizeof(ET) == 2, "split precision runs on fp16 halves");
     constexpr int RN = 16 / (NW * SPLIT), TAPS = 9, LAYOUT = 1, NT = NW * 64;
     static_assert((NW == 8 || NW == 4) && (NW == 8 || SP != 2), "four waves: not the FP8-correction form");
@@ -2360,6 +2364,10 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void net_mfma_kernel(NetA
 #pragma unroll
                     for (int k = 0; k < 4; k++) xf[k] += (float)xl[k] * SPLIT_INV;
                 }
+                if constexpr (ENS) {   // the row as the heads see it (fp32: exact for a 16-bit image, hi + lo for a split one), for ensemble_heads_kernel
+                    if (row0 + NW * u < HROWS && row / NN < valid_boards)
+                        *reinterpret_cast<f32x4*>(a.ens_act + (m0 + row) * FILTERS + lane * 4) = f32x4{xf[0], xf[1], xf[2], xf[3]};
+                }
                 dv[u] = 0.f;
                 du[u] = 0.f;
 #pragma unroll
@@ -2664,6 +2672,81 @@ __global__ void plain_variance_kernel(const float* ube, const float* local, cons
     if (pos >= count) return;
     const float loc = local ? local[pos] : 0.f;
     variance[pos] = fminf(fmaxf(fmaxf(expf(ube[pos]), loc), 0.f), 4.f);
+}
+
+// The sixteen value heads of TZ_ARCH_NET4_ENSEMBLE (net4_ensemble.rs:146-171) and their population variance (:225-233), one
+// workgroup per board: thread (square s, head h) takes conv1x1(256->1) of its square in fp32 - channel c goes to partial sum c & 3,
+// each partial in channel order by fmaf, combined as (p0 + p1) + (p2 + p3) - then bias and ReLU; thread h then runs Linear(16->1)
+// in square order, its bias and tanh, and thread 0 the two-pass variance m = (sum v) / 16, var = (sum (v - m)^2) / 16 in head
+// order.  One arithmetic for every precision and launch form: the image arrives as fp32 (the fused launch's store) or in the
+// storage type (the tower's output), and an exactly representable image gives the same bits either way.  Everything after the conv
+// goes through ens_add / ens_sub / ens_mul, which no FMA contraction reaches (this unit compiles with contraction on).  ens_w: [c][h]
+// conv weights, [h][s] linear weights, 16 conv biases, 16 linear biases.  The variance rule follows at once: clamp(max(e^ube, var_16),
+// 0, 4) with tz_expf (tz_math.h: the exponential the tree kernels and tz_device_math use, the same bits under any compiler flag), so
+// that the variance is a stated function of the values and the UBE this launch's caller can read back.  `var16` keeps var_16.
+__device__ __forceinline__ float ens_add(float x, float y) {
+    _Pragma("clang fp contract(off)")
+    return x + y;
+}
+__device__ __forceinline__ float ens_sub(float x, float y) {
+    _Pragma("clang fp contract(off)")
+    return x - y;
+}
+__device__ __forceinline__ float ens_mul(float x, float y) {
+    _Pragma("clang fp contract(off)")
+    return x * y;
+}
+constexpr int ENS_HEADS = TZ_ENSEMBLE_SIZE, ENS_NN = 16, ENS_W_FLOATS = FILTERS * ENS_HEADS + ENS_HEADS * ENS_NN + 2 * ENS_HEADS;
+template <typename T>
+__global__ __launch_bounds__(256) void ensemble_heads_kernel(const T* act, const float* ens_w, const int32_t* count_dev, int count_host,
+                                                             float* values, float* var16, const float* ube, float* variance) {
+    static_assert(ENS_HEADS == 16, "ensemble_heads_kernel: thread = (square, head) of a 4x4 board and sixteen heads");
+    __shared__ float xs[ENS_NN][FILTERS + 4];   // the board's image; rows 4 banks apart: the four squares of a wave read four banks
+    __shared__ float ws[FILTERS][ENS_HEADS];
+    __shared__ float pre[ENS_HEADS][ENS_NN + 1];
+    __shared__ float vals[ENS_HEADS];
+    const int count = count_dev ? *count_dev : count_host;
+    const int pos = blockIdx.x, tid = threadIdx.x;
+    if (pos >= count) return;
+    const T* img = act + (size_t)pos * ENS_NN * FILTERS;
+    for (int i = tid; i < ENS_NN * FILTERS; i += 256) {
+        xs[i / FILTERS][i % FILTERS] = (float)img[i];
+        ws[i / ENS_HEADS][i % ENS_HEADS] = ens_w[i];
+    }
+    __syncthreads();
+    const int h = tid & 15, s = tid >> 4;
+    float p[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < FILTERS; c += 4) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) p[k] = fmaf(xs[s][c + k], ws[c + k][h], p[k]);
+    }
+    const float* lw = ens_w + FILTERS * ENS_HEADS;
+    const float* cb = lw + ENS_HEADS * ENS_NN;
+    const float* lb = cb + ENS_HEADS;
+    const float d = ens_add(ens_add(ens_add(p[0], p[1]), ens_add(p[2], p[3])), cb[h]);
+    pre[h][s] = d > 0.f ? d : 0.f;
+    __syncthreads();
+    if (tid < ENS_HEADS) {
+        float acc = 0.f;
+        for (int px = 0; px < ENS_NN; px++) acc = ens_add(acc, ens_mul(pre[tid][px], lw[tid * ENS_NN + px]));
+        const float v = tanhf(ens_add(acc, lb[tid]));
+        vals[tid] = v;
+        values[(size_t)pos * ENS_HEADS + tid] = v;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float sum = vals[0];
+        for (int i = 1; i < ENS_HEADS; i++) sum = ens_add(sum, vals[i]);
+        const float m = ens_mul(sum, 0.0625f);
+        float sq = 0.f;
+        for (int i = 0; i < ENS_HEADS; i++) {
+            const float dm = ens_sub(vals[i], m);
+            sq = ens_add(sq, ens_mul(dm, dm));
+        }
+        const float var = ens_mul(sq, 0.0625f);
+        var16[pos] = var;
+        variance[pos] = fminf(fmaxf(fmaxf(tz_expf(ube[pos]), var), 0.f), 4.f);   // net4_ensemble.rs:225-233
+    }
 }
 
 // SimHash straight from the packed game states, 8 boards per workgroup (HashNetwork::get_indices, net6_simhash.rs:202-236): the
@@ -3118,6 +3201,7 @@ struct NetWeights {  // everything tz_net_load_weights replaces, so a failed loa
     float* rndb[3] = {nullptr, nullptr, nullptr};
     float rnd_min = 0.f, rnd_max = 1.f;
     float* simhash = nullptr;
+    float* ens_w = nullptr;
 };
 
 void free_weights(NetWeights& w) {
@@ -3147,6 +3231,8 @@ void free_weights(NetWeights& w) {
     }
     if (w.simhash) (void)hipFree(w.simhash);
     w.simhash = nullptr;
+    if (w.ens_w) (void)hipFree(w.ens_w);
+    w.ens_w = nullptr;
 }
 
 int build_weights(tz_net* net, const TensorMap& m, NetWeights& W) {
@@ -3297,6 +3383,22 @@ int build_weights(tz_net* net, const TensorMap& m, NetWeights& W) {
         else rc = get_tensor(m, "simhash_matrix", (size_t)cin * nn * 32, w);
         if (rc) return rc;
         if ((rc = upload(w, &W.simhash))) return rc;
+    }
+    if (net->has_ens) {   // root / format!("ensemble head {i}"), net4_ensemble.rs:107-131: the value head's graph sixteen times
+        std::vector<float> ew((size_t)ENS_W_FLOATS);
+        float* lw = ew.data() + FILTERS * ENS_HEADS;
+        for (int h = 0; h < ENS_HEADS; h++) {
+            const std::string p = "ensemble head " + std::to_string(h);
+            if ((rc = get_tensor(m, p + ".conv2d.weight", FILTERS, w))) return rc;
+            for (int c = 0; c < FILTERS; c++) ew[(size_t)c * ENS_HEADS + h] = w[c];
+            if ((rc = get_tensor(m, p + ".linear.weight", nn, w))) return rc;
+            for (int px = 0; px < nn; px++) lw[h * ENS_NN + px] = w[px];
+            if ((rc = get_tensor(m, p + ".conv2d.bias", 1, t1))) return rc;
+            lw[ENS_HEADS * ENS_NN + h] = t1[0];
+            if ((rc = get_tensor(m, p + ".linear.bias", 1, t1))) return rc;
+            lw[ENS_HEADS * ENS_NN + ENS_HEADS + h] = t1[0];
+        }
+        if ((rc = upload(ew, &W.ens_w))) return rc;
     }
     return TZ_OK;
 }
@@ -3501,14 +3603,15 @@ constexpr int NET_SPLIT_MAX_GROUPS = 64;           // several CUs per board grou
 constexpr size_t NET_SPLIT_PLANE_BYTES = 7680;     // the largest image plane of those forms (5x5, 4 boards: 120 rows of 64 B)
 constexpr int NET_SPLIT_MAX_POSITIONS = 4 * NET_SPLIT_MAX_GROUPS;   // 64 groups of 1, 2 or 4 boards (with 8 the one-CU forms are faster: 0.63 against 0.69 ms per simulation of 512 games)
 
-template <int NB, int RNP, typename ET, bool PERM, int P = ppt_for(NB), int SP = 0, int ABL = 0, int TT = 0, int NW = 8, int SPLIT = 1>
+template <int NB, int RNP, typename ET, bool PERM, int P = ppt_for(NB), int SP = 0, int ABL = 0, int TT = 0, int NW = 8, int SPLIT = 1, bool ENS = false>
 int launch_net(const NetArgs& a, int max_positions, hipStream_t st) {
     constexpr int RT = RowMap<NB, P, PERM>::RT, LROWS = RT * 16 + 8;
     constexpr bool ROWTAB = SP != 0 && NB == 6 && P == 4;   // as in the kernel: 8-bit table, no remainder planes
     constexpr size_t tap_bytes = TT ? (size_t)9 * RT * RowMap<NB, P, PERM>::PPT * sizeof(int) : (size_t)9 * RT * 64 * (ROWTAB ? 1 : SP == 2 ? sizeof(uint16_t) : sizeof(int));
     constexpr size_t smem = (size_t)LROWS * LDS_ROWB * (SP == 2 ? (NB == 6 ? 16 : 20) : SP ? 16 : 8) + 2 * RT * 16 * sizeof(float) + tap_bytes + (SPLIT > 1 ? 16 : 0);  // image + head scratch + tap table (+ the exchange's flag)
     static_assert(smem <= 160 * 1024, "net kernel: the LDS image does not fit a CU");
-    auto kern = net_mfma_kernel<NB, P, RNP, ET, PERM, SP, ABL, TT, NW, SPLIT>;
+    auto kern = net_mfma_kernel<NB, P, RNP, ET, PERM, SP, ABL, TT, NW, SPLIT, ENS>;
+    if (ENS && !a.ens_act) return tz_fail(TZ_EINVAL, "net launch: the ensemble net's image buffer is missing");
     static bool attr_done[64] = {};   // per device: a function attribute belongs to the device's copy of the module
     int attr_dev = 0;
     TZ_HIP(hipGetDevice(&attr_dev));
@@ -3561,6 +3664,11 @@ int net_small_p(int max_positions) {
 // compile side by side (tz_nn_split.hip includes this file with TZ_NN_SPLIT_TU defined); `net_args` is the caller's NetArgs.
 int tz_nn_launch_split(int sp, int n, const void* net_args, int max_positions, hipStream_t st) {
     const NetArgs& a = *static_cast<const NetArgs*>(net_args);
+    if (a.ens_act) {   // TZ_ARCH_NET4_ENSEMBLE: the 4x4 forms below in an instantiation of their own, which also stores the last image
+        if (n != 4) return tz_fail(TZ_EINVAL, "net: the ensemble net is 4x4");
+        return sp == 1 ? launch_net<4, 1, _Float16, false, 6, 1, 0, 0, 8, 1, true>(a, max_positions, st)
+                       : launch_net<4, 1, _Float16, false, 6, 2, 0, 0, 8, 1, true>(a, max_positions, st);
+    }
     if (sp == 1) {
         // split precision: hi and lo planes share the 160 KB, so half the boards per workgroup (5x5: 4 boards, square-major
         // rows, 14 of 63 (tap, tile) pairs skipped; the other sizes board-major)
@@ -3609,6 +3717,9 @@ template <typename ET>
 int net_fused_et(tz_net* net, const NetArgs& a, int max_positions, hipStream_t st) {
     const bool sq = net_square_major();
     const int small = net_small_p(max_positions);
+    // TZ_ARCH_NET4_ENSEMBLE: the full-size 4x4 form in an instantiation of its own, which also stores the last image (net_fused keeps
+    // it out of the several-CU forms, where a CU holds a quarter of the channels: same bits, one CU per 12 boards)
+    if (net->has_ens) return launch_net<4, 1, ET, false, ppt_for(4), 0, 0, 0, 8, 1, true>(a, max_positions, st);
     // the Agent surface at the reference's batch (tz_net_eval, count known on the host): four CUs per board group
     if (net->n == 5 && a.xch && max_positions <= NET_SPLIT_MAX_POSITIONS && sizeof(ET) == 2) {   // 64 groups x 4 CUs: 1, 2 or 4 boards per group
         if (max_positions <= NET_SPLIT_MAX_GROUPS) return launch_net<5, 1, ET, false, 1, 0, 0, 0, 4, 4>(a, max_positions, st);
@@ -3713,8 +3824,9 @@ int net_fused(tz_net* net, const tz_state* states, const int32_t* gidx, const in
     // and searches of such widths (the reference's selfplay runs 128 games: selfplay/src/main.rs:37).  TZ_NET_SPLIT=0: one CU per group (A/B)
     a.xch = nullptr;
     a.xch_count = nullptr;
+    a.ens_act = net->has_ens ? net->ens_act : nullptr;
     static const bool split_off = getenv("TZ_NET_SPLIT") && !strcmp(getenv("TZ_NET_SPLIT"), "0");
-    const bool split16 = (net->precision == TZ_PREC_F16 || net->precision == TZ_PREC_BF16) &&
+    const bool split16 = !net->has_ens && (net->precision == TZ_PREC_F16 || net->precision == TZ_PREC_BF16) &&
                          ((net->n == 5 && max_positions <= NET_SPLIT_MAX_POSITIONS) || ((net->n == 6 || net->n == 4) && max_positions <= 2 * NET_SPLIT_MAX_GROUPS));
     const bool splitx2 = net->precision == TZ_PREC_F16X2 && net->n == 5 && max_positions <= NET_SPLIT_MAX_POSITIONS;   // the tolerance-holding arithmetic at the reference's batch
     if (!split_off && (split16 || splitx2)) {
@@ -3806,7 +3918,7 @@ int tz_net_ensure_batch(tz_net* net, int batch) {
     net->max_batch = 0;               // ... and nothing may run on them if an allocation below fails
     void** bufs[] = {&net->act_a, &net->act_b, &net->act_c, (void**)&net->planes, (void**)&net->policy_out,
                      (void**)&net->value, (void**)&net->ube, (void**)&net->variance, (void**)&net->aux,
-                     &net->rnd_in, &net->rnd_h1, &net->rnd_h2, (void**)&net->rnd_out, &net->seeds};
+                     &net->rnd_in, &net->rnd_h1, &net->rnd_h2, (void**)&net->rnd_out, &net->seeds, (void**)&net->ens_act, (void**)&net->ens_values};
     for (auto b : bufs) {
         if (*b) (void)hipFree(*b);
         *b = nullptr;
@@ -3823,6 +3935,10 @@ int tz_net_ensure_batch(tz_net* net, int batch) {
     TZ_HIP(hipMalloc(&net->variance, batch * sizeof(float)));
     TZ_HIP(hipMalloc(&net->aux, batch * sizeof(float)));
     if (net->precision == TZ_PREC_F16C6) TZ_HIP(hipMalloc(&net->seeds, tz_nn_c6_seed_bytes(net->n, batch)));
+    if (net->has_ens) {   // freed and replaced with the rest above: a capture that names them is stale by the same bump
+        TZ_HIP(hipMalloc(&net->ens_act, rows * FILTERS * sizeof(float)));
+        TZ_HIP(hipMalloc(&net->ens_values, (size_t)batch * ENS_HEADS * sizeof(float)));
+    }
     if (net->has_rnd) {
         const size_t in_pad = (size_t)(net->cin * net->nn + 31) / 32 * 32;
         TZ_HIP(hipMalloc(&net->rnd_in, (size_t)batch * in_pad * esz));
@@ -3844,6 +3960,7 @@ int tz_net_forward_device(tz_net* net, const tz_state* states, const int32_t* gi
     const bool need_planes = !bf;   // the MFMA path builds its planes in LDS; SimHash reads the packed states (simhash_state_kernel)
     if (need_planes && (rc = encode(net, states, gidx, count_dev, count_host, max_positions, st))) return rc;
     void *x = net->act_a, *t = net->act_b, *y = net->act_c;
+    const void* last = nullptr;   // the tower's output where a launch of its own left it in global memory (the ensemble heads read it)
     const bool split = prec_is_split(net->precision);
     const int rnd_in_pad = (net->cin * nn + 31) / 32 * 32;
     // tz_net_eval at small batches (several CUs per board group): the RND MLP does not wait for the net kernel — it reads the packed
@@ -3945,6 +4062,7 @@ int tz_net_forward_device(tz_net* net, const tz_state* states, const int32_t* gi
             heads_kernel<_Float16><<<max_positions, 64, 0, st>>>((const _Float16*)x, net->heads, count_dev, count_host, nn, net->value, net->ube);
         else
             heads_kernel<__bf16><<<max_positions, 64, 0, st>>>((const __bf16*)x, net->heads, count_dev, count_host, nn, net->value, net->ube);
+        last = x;
     } else {
         float *fx = (float*)x, *ft = (float*)t, *fy = (float*)y;
         if ((rc = conv_f32(net, net->conv_in, net->planes, net->cin, count_dev, count_host, max_positions, nullptr, fx, FILTERS,
@@ -3963,9 +4081,17 @@ int tz_net_forward_device(tz_net* net, const tz_state* states, const int32_t* gi
                            net->pol_stride, false, true, st)))
             return rc;
         heads_kernel<float><<<max_positions, 64, 0, st>>>(fx, net->heads, count_dev, count_host, nn, net->value, net->ube);
+        last = fx;
     }
     // local uncertainty
-    if (net->has_rnd) {
+    if (net->has_ens) {   // var over the sixteen extra heads (net4_ensemble.rs:225-233), from the image the trunk left behind
+        // the fused launch stored it as fp32 (net_mfma_kernel ENS); the other forms leave the tower's output in the storage type
+        if (!last) ensemble_heads_kernel<float><<<max_positions, 256, 0, st>>>(net->ens_act, net->ens_w, count_dev, count_host, net->ens_values, net->aux, net->ube, net->variance);
+        else if (!bf) ensemble_heads_kernel<float><<<max_positions, 256, 0, st>>>((const float*)last, net->ens_w, count_dev, count_host, net->ens_values, net->aux, net->ube, net->variance);
+        else if (prec_is_f16(net->precision))
+            ensemble_heads_kernel<_Float16><<<max_positions, 256, 0, st>>>((const _Float16*)last, net->ens_w, count_dev, count_host, net->ens_values, net->aux, net->ube, net->variance);
+        else ensemble_heads_kernel<__bf16><<<max_positions, 256, 0, st>>>((const __bf16*)last, net->ens_w, count_dev, count_host, net->ens_values, net->aux, net->ube, net->variance);
+    } else if (net->has_rnd) {
         const int in_size = net->cin * nn, in_pad = (in_size + 31) / 32 * 32;
         float* outs[2] = {net->rnd_out, net->rnd_out + (size_t)net->max_batch * 512};
         if (bf) {
@@ -4021,7 +4147,7 @@ int tz_net_create(int board_n, int arch, int device_id, int precision, int block
     if (arch == TZ_ARCH_NET5) n = 5;
     else if (arch == TZ_ARCH_NET4_SIMHASH) n = 4;
     else if (arch == TZ_ARCH_NET6_SIMHASH) n = 6;
-    else if (arch == TZ_ARCH_NET4_LCGHASH) n = 4;
+    else if (arch == TZ_ARCH_NET4_LCGHASH || arch == TZ_ARCH_NET4_ENSEMBLE) n = 4;
     else if (arch != TZ_ARCH_TEST) return tz_fail(TZ_EINVAL, "tz_net_create: unknown architecture");
     if (board_n && board_n != n) return tz_fail(TZ_EINVAL, "tz_net_create: board size does not match the architecture");
     if (n < 3 || n > 6) return tz_fail(TZ_EINVAL, "tz_net_create: board size must be 3..6");
@@ -4048,6 +4174,7 @@ int tz_net_create(int board_n, int arch, int device_id, int precision, int block
     net->ppt = ppt_for(n);
     net->has_rnd = arch == TZ_ARCH_NET5;
     net->has_hash = arch == TZ_ARCH_NET4_SIMHASH || arch == TZ_ARCH_NET6_SIMHASH || arch == TZ_ARCH_NET4_LCGHASH;
+    net->has_ens = arch == TZ_ARCH_NET4_ENSEMBLE;
     if (hipStreamCreate(&net->stream) != hipSuccess) {
         delete net;
         return tz_fail(TZ_EDEVICE, "tz_net_create: hipStreamCreate failed");
@@ -4118,6 +4245,8 @@ static int net_commit_pending(tz_net* net, tz_pending_weights* p) {
         net->rndb[l] = W.rndb[l];
     }
     old.simhash = net->simhash;
+    old.ens_w = net->ens_w;
+    net->ens_w = W.ens_w;
     net->conv_in = W.conv_in;
     net->policy = W.policy;
     net->res = W.res;
@@ -4379,6 +4508,11 @@ int tz_net_init_random(tz_net* net, uint64_t seed) {
         }
         init_const(st, "min", 1, 0.f);
         init_const(st, "max", 1, 1.f);
+    }
+    for (int h = 0; net->has_ens && h < ENS_HEADS; h++) {   // the value head's initialisers, keyed by each head's own names
+        const std::string p = "ensemble head " + std::to_string(h);
+        init_conv(st, seed, p + ".conv2d", 1, FILTERS, 1, true);
+        init_linear(st, seed, p + ".linear", 1, nn);
     }
     if (net->arch == TZ_ARCH_NET4_LCGHASH) {   // root.uniform("lcghash_init", [C, N, N], -100, 100), net4_lcghash.rs:131-136
         init_uniform(st, seed, "lcghash_init", {cin, (uint32_t)net->n, (uint32_t)net->n}, -100.0, 100.0);
@@ -4691,9 +4825,11 @@ int tz_net_destroy(tz_net* net) {
         old.rndb[l] = net->rndb[l];
     }
     old.simhash = net->simhash;
+    old.ens_w = net->ens_w;
     free_weights(old);
     void* bufs[] = {net->act_a, net->act_b, net->act_c, net->planes, net->policy_out, net->value, net->ube,
-                    net->variance, net->aux, net->rnd_in, net->rnd_h1, net->rnd_h2, net->rnd_out, net->bitset, net->seeds, net->xch, net->xch_count};
+                    net->variance, net->aux, net->rnd_in, net->rnd_h1, net->rnd_h2, net->rnd_out, net->bitset, net->seeds, net->xch, net->xch_count,
+                    net->ens_act, net->ens_values};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (net->stream_rnd) (void)hipStreamDestroy(net->stream_rnd);
@@ -4954,6 +5090,29 @@ int tz_net_forward_raw(tz_net* net, int batch, const tz_state* states, float* po
     if (dout) (void)hipFree(dout);
     if (rc) return rc;
     if (e != hipSuccess) return tz_fail(TZ_EDEVICE, std::string("tz_net_forward_raw: ") + hipGetErrorString(e));
+    return TZ_OK;
+}
+
+// EnsembleNetwork::forward_core_and_ensemble(xs, false) (net4_ensemble.rs:157-171): the sixteen head values, out[batch][16]
+int tz_net_ensemble_values(tz_net* net, int batch, const tz_state* states, float* out) {
+    if (!net || !states || !out || batch <= 0) return tz_fail(TZ_EINVAL, "tz_net_ensemble_values: bad argument");
+    if (!net->has_ens) return tz_fail(TZ_EINVAL, "tz_net_ensemble_values: not a TZ_ARCH_NET4_ENSEMBLE network");
+    for (int b = 0; b < batch; b++)
+        if (states[b].n != net->n) return tz_fail(TZ_EINVAL, "tz_net_ensemble_values: state board size does not match the network");
+    tz_state* dstates = nullptr;
+    int rc = net_upload_states(net, batch, states, &dstates);
+    if (rc) return rc;
+    hipStream_t st = net->stream;
+    NetOut o;
+    rc = tz_net_forward_device(net, dstates, nullptr, nullptr, batch, batch, st, &o);
+    hipError_t e = hipSuccess;
+    if (!rc) {
+        e = hipMemcpyAsync(out, net->ens_values, (size_t)batch * ENS_HEADS * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    }
+    (void)hipFree(dstates);
+    if (rc) return rc;
+    if (e != hipSuccess) return tz_fail(TZ_EDEVICE, std::string("tz_net_ensemble_values: ") + hipGetErrorString(e));
     return TZ_OK;
 }
 

@@ -636,7 +636,7 @@ int ot_canonical_names(const NamedTensors& in, TensorStore& out) {
 }
 
 void ot_tch_names(const TensorStore& in, NamedTensors& out) {
-    // Creation order of Net::new (net5.rs:152-170, net6_simhash.rs:122-141): core (input conv, batch norm, blocks), policy,
+    // Creation order of Net::new (net5.rs:152-170, net6_simhash.rs:122-141, net4_ensemble.rs:107-131): core (input conv, batch norm, blocks), policy,
     // value, ube, then the uncertainty side nets.  A path that already exists gets `__<variables registered so far>`
     // (tch nn::Path::add).  Inside nn::batch_norm, tch creates weight and bias (the `affine` pair) before running_mean and
     // running_var; TZ_TCH_BN_ORDER=stats_first gives the older order.  Neither is pinned by a file of the reference (none is
@@ -683,6 +683,14 @@ void ot_tch_names(const TensorStore& in, NamedTensors& out) {
     for (const char* r : rest) {
         add(r, r);
         done[r] = true;
+    }
+    for (int h = 0;; h++) {   // root / format!("ensemble head {i}") after ube (net4_ensemble.rs:107-131): head order, not name order
+        const std::string p = "ensemble head " + std::to_string(h);
+        if (!in.count(p + ".conv2d.weight")) break;
+        for (const char* v : {".conv2d.weight", ".conv2d.bias", ".linear.weight", ".linear.bias"}) {
+            add(p + v, p + v);
+            done[p + v] = true;
+        }
     }
     for (auto& kv : in)   // anything else the store holds, in name order
         if (kv.first.compare(0, 5, "core.") && !done.count(kv.first)) add(kv.first, kv.first);

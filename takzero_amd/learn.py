@@ -46,6 +46,11 @@ class Trainer:
     RND_NAMES = tuple("rnd_learning.%s.%s" % (layer, part) for layer in ("input_linear", "hidden_linear", "final_linear")
                       for part in ("weight", "bias"))
 
+    # the variables of net4_ensemble's sixteen heads (net4_ensemble.rs:107-131): trained by the step while ensemble targets are
+    # set, and then readable / writable through tensor() like the names of `names`
+    ENSEMBLE_NAMES = tuple("ensemble head %d.%s" % (i, part) for i in range(api.ENSEMBLE_SIZE)
+                           for part in ("conv2d.weight", "conv2d.bias", "linear.weight", "linear.bias"))
+
     def __init__(self, arch=api.ARCH_NET5, n=0, blocks=0, batch=BATCH_SIZE, lr=LEARNING_RATE, device=0):
         from . import weights as W
 
@@ -121,6 +126,12 @@ class Trainer:
             out = np.zeros(shape, np.float32)
             check(self.lib.tz_trainer_get_tensor(self.h, name.encode(), what, out.ctypes.data, out.size))
             return out
+        if name in self.ENSEMBLE_NAMES:
+            shape = {"conv2d.weight": (1, 256, 1, 1), "conv2d.bias": (1,), "linear.weight": (1, self.n * self.n),
+                     "linear.bias": (1,)}[name.split(".", 1)[1]]
+            out = np.zeros(shape, np.float32)
+            check(self.lib.tz_trainer_get_tensor(self.h, name.encode(), what, out.ctypes.data, out.size))
+            return out
         out = np.zeros(self.names[name], np.float32)
         check(self.lib.tz_trainer_get_tensor(self.h, name.encode(), what, out.ctypes.data, out.size))
         return out.reshape(self.shapes.get(name, out.shape))
@@ -168,6 +179,24 @@ class Trainer:
                                                 C.byref(mn), C.byref(mx)))
         return float(mn.value), float(mx.value)
 
+    def set_ensemble_targets(self, targets):
+        """tz_trainer_set_ensemble_targets: [batch, 16] targets arm the trainer (every later step also trains the sixteen heads,
+        eee/src/ensemble.rs:318-351); None disarms it."""
+        if targets is None:
+            check(self.lib.tz_trainer_set_ensemble_targets(self.h, None))
+            return self
+        t = np.ascontiguousarray(targets, np.float32)
+        if t.shape != (self.batch, api.ENSEMBLE_SIZE):
+            raise ValueError("set_ensemble_targets: want [%d, %d] targets" % (self.batch, api.ENSEMBLE_SIZE))
+        check(self.lib.tz_trainer_set_ensemble_targets(self.h, t.ctypes.data))
+        return self
+
+    def ensemble_last(self):
+        """(loss_ensemble, the heads' values [batch, 16]) of the last armed step, before that step's update."""
+        loss, values = C.c_float(), np.zeros((self.batch, api.ENSEMBLE_SIZE), np.float32)
+        check(self.lib.tz_trainer_ensemble_last(self.h, C.byref(loss), values.ctypes.data))
+        return float(loss.value), values
+
     def extras(self):
         """The variables the step never touches (RND nets, SimHash matrix, lcghash_init), as the library carries them."""
         from .weights import loads_tzw
@@ -184,8 +213,11 @@ class Trainer:
         out.update(self.extras())
         return out
 
-    def step(self, states, policy, mask, value, ube, train_ube=True, apply=True):
-        """compute_loss_and_take_step -> (loss_policy, loss_value, loss_ube)."""
+    def step(self, states, policy, mask, value, ube, train_ube=True, apply=True, ensemble_targets=None):
+        """compute_loss_and_take_step -> (loss_policy, loss_value, loss_ube).  `ensemble_targets` [batch, 16] (net4_ensemble) arm the
+        trainer for this and later steps (set_ensemble_targets; loss_ensemble through ensemble_last)."""
+        if ensemble_targets is not None:
+            self.set_ensemble_targets(ensemble_targets)
         st = api._states(states)
         B = self.batch
         out = api.policy_size(self.n)
@@ -211,6 +243,50 @@ class Trainer:
         out = np.zeros((self.batch, self.n * self.n, 256), np.float32)
         check(self.lib.tz_trainer_activation(self.h, layer, out.ctypes.data, out.size))
         return out
+
+
+def sample_actions(policies, draws):
+    """choose_weighted with the randomness handed in (eee/src/ensemble.rs:274-280): for every (move indices, probabilities) pair the first
+    action whose cumulative probability passes draw * total, draw in [0, 1).  Returns the move indices, uint16."""
+    draws = np.asarray(draws, np.float64)
+    assert draws.shape == (len(policies),)
+    actions = np.zeros(len(policies), np.uint16)
+    for i, (moves, probs) in enumerate(policies):
+        cum = np.cumsum(np.asarray(probs, np.float64))
+        k = int(np.searchsorted(cum, draws[i] * cum[-1], side="right"))
+        actions[i] = np.asarray(moves)[min(k, len(cum) - 1)]
+    return actions
+
+
+def ensemble_targets(net, mcts, states, policies, draws):
+    """get_ensemble_targets (eee/src/ensemble.rs:265-316): for every position an action drawn in proportion to its improved policy, one
+    step of the game, and -DISCOUNT_FACTOR * the net's sixteen head values there; where the step ended the game all sixteen entries are
+    f32::from(Eval::from(terminal).negate()) instead (eval.rs:40-47, 95-105: a game the mover has won is Loss(0) for the side to move,
+    negated Win(1) = 0.997; a draw is 0).  `policies[i]` = (move indices, probabilities) of position i; `draws[i]` in [0, 1) picks the
+    action (sample_actions; the randomness stays with the caller).  `mcts` is a scratch
+    search handle of the same board size: its positions are replaced.  Returns [B, 16] fp32."""
+    st = api._states(states)
+    B, W = len(st), mcts.batch
+    assert len(policies) == B
+    actions = sample_actions(policies, draws)
+    out = np.zeros((B, api.ENSEMBLE_SIZE), np.float32)
+    for lo in range(0, B, W):
+        k = min(W, B - lo)
+        chunk, act = np.repeat(st[lo:lo + 1], W), np.full(W, 0xFFFF, np.uint16)
+        chunk[:k], act[:k] = st[lo:lo + k], actions[lo:lo + k]
+        mcts.set_positions(np.arange(W), chunk)
+        ok = mcts.play_moves(act)
+        if not np.all(ok[:k] == 1):
+            raise ValueError("ensemble_targets: the sampled action of position %d is not legal there" % (lo + int(np.argmax(ok[:k] != 1))))
+        after = mcts.get_positions()[:k]
+        out[lo:lo + k] = -api.DISCOUNT_FACTOR * net.ensemble_values(after)
+        ended = mcts.restart_terminal_envs(np.zeros(W, np.int32))[:k] != api.TERMINAL_NONE
+        _reason, winner = mcts.terminal_details()
+        for i in np.flatnonzero(ended):
+            # the terminal as the side to move after the step sees it, negated: one ply further, from the other side
+            sign = 0.0 if winner[i] == 2 else (-1.0 if winner[i] == after["to_move"][i] else 1.0)
+            out[lo + i] = api.DISCOUNT_FACTOR * np.float32(sign)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------

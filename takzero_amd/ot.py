@@ -70,7 +70,7 @@ def load_ot_libtorch(path):
 
 def tch_names(tensors):
     """The inverse (what tch would name the variables when it builds the net: creation order of net5.rs /
-    net6_simhash.rs / net4_lcghash.rs, duplicates suffixed with the number of variables registered so far).  Used to write test
+    net6_simhash.rs / net4_lcghash.rs / net4_ensemble.rs, duplicates suffixed with the number of variables registered so far).  Used to write test
     archives; the reader above does not depend on the exact numbers."""
     out, count = [], 0
     seen = set()
@@ -146,7 +146,7 @@ def save_ot_libtorch(path, tensors):
                 raw = os.path.join(tmp, "t%d.bin" % i)
                 a = np.ascontiguousarray(arr, np.float32)
                 a.tofile(raw)
-                mf.write("%s %d %s %s\n" % (name, a.ndim, " ".join(str(d) for d in a.shape), raw))
+                mf.write("%s\t%d %s %s\n" % (name, a.ndim, " ".join(str(d) for d in a.shape), raw))
         part = path + ".part"
         # the archive writer is a background helper: one thread, low priority, so that it never competes with the
         # threads that feed the GPU

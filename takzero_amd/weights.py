@@ -11,7 +11,7 @@ reference creates under one path, residual.rs:50-55) are spelled `.a.` and `.b.`
     u16 name length, name (utf-8), u8 ndim, u32 dims[ndim], f32 data (little endian, C order)
 
 Architectures: net5 (takzero/src/network/net5.rs:44-148), net4_simhash /
-net6_simhash (net6_simhash.rs:43-141), net4_lcghash (net4_lcghash.rs:39-140).  `init_weights` follows tch's defaults as the reference
+net6_simhash (net6_simhash.rs:43-141), net4_lcghash (net4_lcghash.rs:39-140), net4_ensemble (net4_ensemble.rs:39-131).  `init_weights` follows tch's defaults as the reference
 relies on them: conv/linear weights Kaiming-uniform(a=sqrt 5), biases U(+-1/sqrt(fan_in)),
 BatchNorm weight U(0,1), bias 0, running stats 0/1, RND min 0 / max 1 (net5.rs:166-168).
 """
@@ -23,6 +23,8 @@ ARCH_NET4_SIMHASH = 4
 ARCH_NET5 = 5
 ARCH_NET6_SIMHASH = 6
 ARCH_NET4_LCGHASH = 14
+ARCH_NET4_ENSEMBLE = 24
+ENSEMBLE_SIZE = 16
 ARCH_TEST = 100
 FILTERS = 256
 HASH_BITS = 32
@@ -39,11 +41,11 @@ def output_channels(n):
 
 
 def arch_blocks(arch, blocks=0):
-    return {ARCH_NET5: 20, ARCH_NET4_SIMHASH: 16, ARCH_NET6_SIMHASH: 16, ARCH_NET4_LCGHASH: 16}.get(arch, blocks)
+    return {ARCH_NET5: 20, ARCH_NET4_SIMHASH: 16, ARCH_NET6_SIMHASH: 16, ARCH_NET4_LCGHASH: 16, ARCH_NET4_ENSEMBLE: 16}.get(arch, blocks)
 
 
 def arch_board(arch, n=0):
-    return {ARCH_NET5: 5, ARCH_NET4_SIMHASH: 4, ARCH_NET6_SIMHASH: 6, ARCH_NET4_LCGHASH: 4}.get(arch, n)
+    return {ARCH_NET5: 5, ARCH_NET4_SIMHASH: 4, ARCH_NET6_SIMHASH: 6, ARCH_NET4_LCGHASH: 4, ARCH_NET4_ENSEMBLE: 4}.get(arch, n)
 
 
 def save_tzw(path, tensors):
@@ -135,6 +137,11 @@ def init_weights(arch, n=0, blocks=0, seed=123, trained_stats=False):
     for head in ("value", "ube"):
         _conv(rng, t, head + ".conv2d", 1, FILTERS, 1, True)
         _linear(rng, t, head + ".linear", 1, nn)
+    if arch == ARCH_NET4_ENSEMBLE:
+        # root / format!("ensemble head {i}"): the value head's graph sixteen times, after ube (net4_ensemble.rs:107-131)
+        for i in range(ENSEMBLE_SIZE):
+            _conv(rng, t, "ensemble head %d.conv2d" % i, 1, FILTERS, 1, True)
+            _linear(rng, t, "ensemble head %d.linear" % i, 1, nn)
     if arch == ARCH_NET5:
         for net in ("rnd_learning", "rnd_target"):
             _linear(rng, t, net + ".input_linear", RND_HIDDEN, cin * nn)
