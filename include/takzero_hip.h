@@ -45,7 +45,8 @@ extern "C" {
 #define TZ_EPARSE (-2)   /* malformed TPS / PTN / weight file                          */
 #define TZ_EDEVICE (-3)  /* HIP runtime failure (message carries hipGetErrorString)    */
 #define TZ_ENOMEM (-4)   /* host or device allocation failed                           */
-#define TZ_ECAPACITY (-5)/* a per-game node pool or trajectory buffer overflowed       */
+#define TZ_ECAPACITY (-5)/* a per-game node pool or trajectory buffer overflowed, or a  */
+                         /* position has more legal moves than max_actions             */
 #define TZ_ESTATE (-6)   /* call not valid in the current state (e.g. noise on an      */
                          /* un-expanded root — batched.rs / noise.rs:12-15 assert)     */
 #define TZ_ENUMERIC (-7) /* NaN produced by the net (reference panics: net5.rs:263)    */
@@ -214,7 +215,24 @@ int tz_net_save_bitset(tz_net* net, const char* path);
 int tz_search_create(tz_net* net, int agent_kind, int batch, int board_n, int half_komi,
                      int node_capacity, tz_search** out);
 int tz_search_destroy(tz_search* s);
-/* BATCH_SIZE, N, HALF_KOMI of the handle and the widest child list it can hold */
+/* BATCH_SIZE, N, HALF_KOMI of the handle and the widest child list it can hold.
+ *
+ * max_actions is 64 on 3x3, 192 on 4x4, 512 on 5x5 and 1024 on 6x6.  The reference's child lists are Vecs and have no limit;
+ * positions with more legal moves exist on every board size (tall stacks under the mover's control; none is near the games the
+ * reference plays).  The Agent surface, tz_net_eval, takes its own amax and evaluates such positions like any other.  A search
+ * handle does this with them:
+ *   - tz_search_set_positions accepts any position: it generates no moves.
+ *   - When a simulation reaches a node with more than max_actions legal moves, at the root or below it, that node is not
+ *     expanded and gets no children, then or later; nothing is written past a row, and tz_search_pool_overflows does not count it.
+ *     The visits along the path to it are counted without a backup, so the tree of that game is worth nothing from then on.
+ *   - tz_search_simulate and tz_search_simulate_batch still run all their simulations or rounds and then return TZ_ECAPACITY
+ *     with a text that names max_actions; every other game of the batch is exactly what it would be had the call succeeded.
+ *     The report clears the condition, and each later call that reaches such a node reports it again.
+ *   - tz_search_gumbel_sh returns the same error at its first simulation (an over-wide root) or at the end of the halving step in
+ *     which a node below the root was reached; it selects nothing, and the trees keep the simulations made until then.
+ *   - tz_search_set_positions over the game in question puts the handle back: from there it behaves like a fresh handle with the
+ *     same history, with or without captured graphs.  After the error from tz_search_gumbel_sh, set every game again before the
+ *     halving is repeated (the other games are part of the way through it). */
 int tz_search_shape(tz_search* s, int* batch_out, int* board_n_out, int* half_komi_out, int* max_actions_out);
 /* nodes_and_envs_mut: overwrite envs and reset their trees (reanalyze/src/main.rs:159-165). */
 int tz_search_set_positions(tz_search* s, int count, const int32_t* game_idx, const tz_state* states);
@@ -222,7 +240,8 @@ int tz_search_get_positions(tz_search* s, tz_state* states_out /*[batch]*/);
 /* BatchedMCTS::new openings: env.rs:65-79.  opening_choice[g] in [0,16): symmetry*2 + opposite. */
 int tz_search_new_openings(tz_search* s, const int32_t* opening_choice);
 /* BatchedMCTS::simulate called n_sims times (batched.rs:63-128); betas[batch]. Asynchronous
- * on the handle's stream; any later call that returns data synchronises. */
+ * on the handle's stream; any later call that returns data synchronises.  TZ_ECAPACITY "more legal moves than max_actions":
+ * see tz_search_shape. */
 int tz_search_simulate(tz_search* s, const float* betas, int n_sims);
 /* Node::simulate_batch (mcts.rs:268-328) applied to every root of the handle, `rounds` times: the search of the reference's tei and
  * analysis binaries (tei/src/main.rs:253, analysis/src/main.rs:35,78), which fills a network batch from one tree.  Per tree and
@@ -312,7 +331,10 @@ int tz_search_restart_terminal(tz_search* s, const int32_t* opening_choice, int8
 int tz_search_terminal_details(tz_search* s, int8_t* reason_out, uint8_t* winner_out);
 /* Validated move application without search (Replay::from_str / Replay::states, target.rs:205-212,248-268):
  * actions[g] (0xFFFF = none) is applied to game g iff it is legal there; ok_out[g] = 1 applied, 0 illegal or
- * none, -1 position already terminal.  Trees are reset. */
+ * none, -1 position already terminal.  Trees are reset.  Positions wider than max_actions are handled like any other up to 1024
+ * legal moves, so on every board size but 6x6.  Of a 6x6 position with more, only the moves among the first 1024 or so (whole
+ * squares' worth, in move order) are recognised: such a move is applied; for any other move, legal or not, ok_out[g] is 0, the
+ * position is unchanged and the call returns TZ_ECAPACITY "more legal moves than max_actions" after handling the other games. */
 int tz_search_play_moves(tz_search* s, const uint16_t* actions, int8_t* ok_out);
 /* BatchedMCTS::gumbel_sequential_halving with caller-supplied Gumbel(0,1) samples
  * (batched.rs:207-409): gumbel[batch][amax]; selected_out[batch] move indices. */

@@ -787,8 +787,7 @@ int tz_search_play_moves(tz_search* s, const uint16_t* actions, int8_t* ok_out) 
     int rc = tz_tree_play_moves(s->d, s->act_dev, s->i8_dev, s->stream);
     if (rc) return rc;
     TZ_HIP(hipMemcpyAsync(ok_out, s->i8_dev, s->d.batch, hipMemcpyDeviceToHost, s->stream));
-    TZ_HIP(hipStreamSynchronize(s->stream));
-    return TZ_OK;
+    return check_error_flag(s);  // synchronises; flag 3: a move could not be judged (see the header)
 }
 
 int tz_search_gumbel_sh(tz_search* s, const float* betas, int sampled_actions, int search_budget, const float* gumbel,

@@ -302,6 +302,9 @@ void dirichlet_rows(tz_selfplay* sp, int w) {
 int record(tz_selfplay* sp) {  // take_a_step up to the step itself (selfplay/src/main.rs:238-257)
     int w = 0, rc;
     if ((rc = fetch_children(sp, &w))) return rc;
+    // complete() copies a root's children into rows of sp->amax entries.  A device search refuses such a root before this point
+    // (TZ_ECAPACITY); a search without that limit is refused here, before anything of the move is stored.
+    if (w > sp->amax) return tz_fail(TZ_ECAPACITY, "selfplay: a root has more children than max_actions");
     sp->history.emplace_back();
     MoveRecord& m = sp->history.back();
     const int B = sp->B;
@@ -378,6 +381,7 @@ int complete(tz_selfplay* sp) {  // restart_envs_and_complete_targets (selfplay/
                 // "Only generate targets from non-exploratory episodes (or after the initial exploration)"
                 if (sp->betas[g] == 0.0f || st.ply > WEIGHTED_RANDOM_PLIES) {
                     const int kk = (int)m.nchild[g];
+                    if (kk > amax) return tz_fail(TZ_ECAPACITY, "selfplay: a root has more children than max_actions");  // as in reanalyze
                     sp->t_states.push_back(st);
                     const size_t off = sp->t_moves.size();
                     sp->t_moves.resize(off + amax, 0);
@@ -974,6 +978,8 @@ int tz_reanalyze_iterate(tz_reanalyze* ra) {
     uint64_t total_moves = 0;
     for (int g = 0; g < B; g++) {
         const int nc = (int)info[g].n_children;
+        // a device search refuses such a root before this point (TZ_ECAPACITY); a search without that limit must not overrun the row
+        if (nc > ra->amax) return tz_fail(TZ_ECAPACITY, "reanalyze: a root has more children than max_actions");
         nm[g] = nc;
         total_moves += (uint64_t)nc;
         memcpy(&mv_pad[(size_t)g * ra->amax], &moves[(size_t)g * w], sizeof(uint16_t) * nc);

@@ -110,6 +110,9 @@ __device__ __forceinline__ void children_min_allknown(const SearchDev& s, size_t
         Ev e{s.t.eval_tag[base + node], s.t.eval_bits[base + node]};
         if (node == patch_node) e = patch;
         known = known && ev_known(e);
+        // The same source form was miscompiled in select_best_child (see there): with more than 64 children the loop kept the tag
+        // and the index of the lane's first child.  Here the compiled loop is right; the solved wide roots of
+        // tests/test_gpu_action_capacity.py (a best child beyond the first 64) fail if a compiler does to it what it did there.
         if (best_i == 0x7fffffff || ev_cmp(e, best) < 0) {
             best = e;
             best_i = i;
@@ -409,7 +412,16 @@ __global__ __launch_bounds__(64) void descend_kernel(SearchDev s, int from_start
     // NeedsNetwork: env.populate_actions (batched.rs:84) + hand the leaf position to the net
     uint16_t* acts = s.leaf_act + (size_t)g * s.max_actions;
     const int nact = gen_moves<N>(&env, reach, acts, s.max_actions);
-    if (nact > s.max_actions && l == 0) atomicMax(s.error_flag, 3);
+    if (nact > s.max_actions) {
+        // gen_moves wrote the moves that fit and left the rest of the row as it was: such a leaf is not expanded (its game stands
+        // still until set_positions replaces it), the other games go on
+        if (l == 0) {
+            atomicMax(s.error_flag, 3);
+            s.leaf_kind[g] = 0;
+            s.traj_len[g] = 0;
+        }
+        return;
+    }
     {
         const uint32_t* a = reinterpret_cast<const uint32_t*>(&env);
         uint32_t* b = reinterpret_cast<uint32_t*>(&s.leaf_env[g]);
@@ -418,7 +430,7 @@ __global__ __launch_bounds__(64) void descend_kernel(SearchDev s, int from_start
     for (int i = l; i < depth; i += 64) s.traj[(size_t)g * TZ_MAX_DEPTH + i] = tnode[i];
     if (l == 0) {
         s.leaf_kind[g] = 1;
-        s.leaf_nact[g] = (uint16_t)(nact > s.max_actions ? s.max_actions : nact);
+        s.leaf_nact[g] = (uint16_t)nact;
         s.traj_len[g] = (uint32_t)depth;
     }
 }
@@ -602,7 +614,10 @@ __global__ __launch_bounds__(64) void descend_batch_kernel(SearchDev s, LeafBatc
             const size_t slot = (size_t)g * b.leaves + collected;
             uint16_t* acts = b.act + slot * s.max_actions;
             const int nact = gen_moves<N>(&env, reach, acts, s.max_actions);  // env.populate_actions, mcts.rs:289
-            if (nact > s.max_actions && l == 0) atomicMax(s.error_flag, 3);
+            if (nact > s.max_actions) {  // not collected: the row holds only the moves that fit (see descend_kernel)
+                if (l == 0) atomicMax(s.error_flag, 3);
+                break;
+            }
             {
                 const uint32_t* a = reinterpret_cast<const uint32_t*>(&env);
                 uint32_t* d = reinterpret_cast<uint32_t*>(&b.env[slot]);
@@ -610,7 +625,7 @@ __global__ __launch_bounds__(64) void descend_batch_kernel(SearchDev s, LeafBatc
             }
             for (int i = l; i < depth; i += 64) b.traj[slot * TZ_MAX_DEPTH + i] = tnode[i];
             if (l == 0) {
-                b.nact[slot] = (uint16_t)(nact > s.max_actions ? s.max_actions : nact);
+                b.nact[slot] = (uint16_t)nact;
                 b.traj_len[slot] = (uint32_t)depth;
             }
             collected++;
@@ -931,12 +946,15 @@ __device__ __forceinline__ int select_best_child(const SearchDev& s, size_t base
     if (s.t.eval_tag[node] != TZ_EVAL_VALUE) {  // solved: first minimum child evaluation
         Ev best{0, 0};
         int best_i = 0x7fffffff;
+        // Selects, not a branch around `best = e`: with more than 64 children the branch form was compiled (hipcc of ROCm 7.2, gfx950, -O3)
+        // into a loop whose later iterations replaced best.bits alone and kept the tag and the index of the lane's first child, so
+        // a solved node whose best child lay beyond its first 64 answered with another move (tests/test_gpu_action_capacity.py).
         for (int i = l; i < nc; i += 64) {
             const Ev e{s.t.eval_tag[base + c0 + i], s.t.eval_bits[base + c0 + i]};
-            if (best_i == 0x7fffffff || ev_cmp(e, best) < 0) {
-                best = e;
-                best_i = i;
-            }
+            const bool take = best_i == 0x7fffffff || ev_cmp(e, best) < 0;
+            best.tag = take ? e.tag : best.tag;
+            best.bits = take ? e.bits : best.bits;
+            best_i = take ? i : best_i;
         }
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) {
@@ -1157,11 +1175,18 @@ __global__ __launch_bounds__(64) void play_moves_kernel(SearchDev s, const uint1
         if (l == 0) ok[g] = -1;
         return;
     }
+    // The row holds every move of a position up to 5x5 and of a 6x6 position within max_actions.  Of a wider 6x6 position
+    // gen_moves writes the moves that fit and leaves the rest of the row as it is, hence "no move" in every entry first.  A move
+    // that is not among the written ones of such a position cannot be judged: flag 3, position unchanged.
+    for (int i = l; i < 1024; i += 64) acts[i] = 0xFFFF;
     const int n = gen_moves<N>(&env, reach, acts, 1024);
     bool hit = false;
     for (int i = l; i < n && i < 1024; i += 64) hit = hit || acts[i] == a;
     if (!__any(hit)) {
-        if (l == 0) ok[g] = 0;
+        if (l == 0) {
+            ok[g] = 0;
+            if (n > 1024) atomicMax(s.error_flag, 3);
+        }
         return;
     }
     apply_move<N>(&env, a);
