@@ -83,6 +83,14 @@ impl HipNet {
         check(unsafe { sys::tz_net_ensemble_values(self.raw, states.len() as i32, states.as_ptr(), out.as_mut_ptr() as *mut f32) })?;
         Ok(out)
     }
+    /// `RndNetwork::forward_rnd(xs, false)` (net4_rnd.rs:210-223): the sum of squared differences of the two towers, per position.
+    /// `Err` unless the handle is a `sys::TZ_ARCH_NET4_RND` network.
+    pub fn rnd_raw(&self, envs: &[Env]) -> Result<Vec<f32>, TchError> {
+        let states: Vec<sys::TzState> = envs.iter().map(pack_state).collect();
+        let mut out = vec![0.0f32; states.len()];
+        check(unsafe { sys::tz_net_rnd_raw(self.raw, states.len() as i32, states.as_ptr(), out.as_mut_ptr()) })?;
+        Ok(out)
+    }
 }
 
 impl Drop for HipNet {

@@ -41,7 +41,7 @@ int main(int argc, char** argv) {
     int arch = TZ_ARCH_NET5, n = 5, blocks = 0, leaves = 128, rounds = 8, precision = TZ_PREC_F16, device = 0, half_komi = 4, show = 10;
     unsigned long long seed = 0;
     auto usage = []() {
-        fprintf(stderr, "usage: analysis_cli [--model FILE.ot|.tzw --tps TPS --arch 4|5|6|14|100|net4_simhash|net5|net6_simhash|net4_lcghash|test --n N --blocks K --leaves 128 --rounds 8 --selection puct|uct|improved "
+        fprintf(stderr, "usage: analysis_cli [--model FILE.ot|.tzw --tps TPS --arch 4|5|6|14|24|34|100|net4_simhash|net5|net6_simhash|net4_lcghash|net4_ensemble|net4_rnd|test --n N --blocks K --leaves 128 --rounds 8 --selection puct|uct|improved "
                         "--half-komi 4 --children 10 --seed X --device G --f32|--bf16]\n");
         return 2;
     };

@@ -104,7 +104,7 @@ int main(int argc, char** argv) {
         }
     }
     if (model_path.empty()) {
-        fprintf(stderr, "usage: evaluation_cli --model-path DIR [--step K --opening-book FILE --arch 4|5|6|14|100|net4_simhash|net5|net6_simhash|net4_lcghash|test --n N --blocks K --games 64 "
+        fprintf(stderr, "usage: evaluation_cli --model-path DIR [--step K --opening-book FILE --arch 4|5|6|14|24|34|100|net4_simhash|net5|net6_simhash|net4_lcghash|net4_ensemble|net4_rnd|test --n N --blocks K --games 64 "
                         "--sampled-actions 64 --budget 768 --max-moves 200 --rounds R --seed X --sleep SECONDS --device G --bf16|--f16c6|--f16c8|--f16x2]\n");
         return 2;
     }

@@ -62,7 +62,7 @@ static int on_step(void* user, int64_t step, const float* losses, const tz_state
 
 static const char* USAGE =
     "usage: learn_cli --directory DIR [options]\n"
-    "  --arch 4|5|6|14|100|net4_simhash|net5|net6_simhash|net4_lcghash|test  --n N  --blocks K  --batch B  --steps S  --seed X\n"
+    "  --arch 4|5|6|14|24|34|100|net4_simhash|net5|net6_simhash|net4_lcghash|net4_ensemble|net4_rnd|test  --n N  --blocks K  --batch B  --steps S  --seed X\n"
     "  --pre-training-steps S  --initial-targets T  --steps-before-reanalyze S  --min-selfplay T  --min-reanalyze T\n"
     "  --steps-per-save S  --steps-per-checkpoint S  --read-interval SEC  --sleep SEC  --wait-limit SEC  --verbose\n"
     "  --train-rnd               net5 only: train the RND predictor in every step of the main loop and calibrate min / max\n"

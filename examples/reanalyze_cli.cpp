@@ -133,7 +133,7 @@ int main(int argc, char** argv) {
         }
     }
     if (directory.empty() || selection_rule(selection) < 0) {
-        fprintf(stderr, "usage: reanalyze_cli --directory DIR [--model FILE --watch model_latest.ot --arch 4|5|6|14|100|net4_simhash|net5|net6_simhash|net4_lcghash|test --n N --blocks K --games B "
+        fprintf(stderr, "usage: reanalyze_cli --directory DIR [--model FILE --watch model_latest.ot --arch 4|5|6|14|24|34|100|net4_simhash|net5|net6_simhash|net4_lcghash|net4_ensemble|net4_rnd|test --n N --blocks K --games B "
                         "--sims S --search puct|gumbel --selection puct|uct|improved --sampled-actions K --iterations I --min-positions P --wait-limit SECONDS --seed X "
                         "--rank R --world N --device G --async-reload --bf16|--f16c6|--f16c8|--f16x2]\n");
         return 2;

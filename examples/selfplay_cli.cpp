@@ -142,7 +142,7 @@ int main(int argc, char** argv) {
         }
     }
     if (directory.empty() || selection_rule(selection) < 0 || (world > 1 && comm_kind != "rccl" && comm_kind != "fs")) {
-        fprintf(stderr, "usage: selfplay_cli --directory DIR [--model FILE.ot|.tzw --watch model_latest.ot --arch 4|5|6|14|100|net4_simhash|net5|net6_simhash|net4_lcghash|test --n N --blocks K "
+        fprintf(stderr, "usage: selfplay_cli --directory DIR [--model FILE.ot|.tzw --watch model_latest.ot --arch 4|5|6|14|24|34|100|net4_simhash|net5|net6_simhash|net4_lcghash|net4_ensemble|net4_rnd|test --n N --blocks K "
                         "--games B --sims S --search puct|gumbel --selection puct|uct|improved --sampled-actions K --moves M --exploration --async-reload --f16|--bf16|--f16c6|--f16c8|--f16x2 "
                         "--wait-limit SECONDS --seed X] [--rank R --world N --comm rccl|fs --comm-dir D --device G]\n");
         return 2;

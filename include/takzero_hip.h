@@ -90,7 +90,7 @@ typedef struct tz_state {
 typedef struct tz_net tz_net;       /* opaque: a network on one GPU  (Network + Agent impl)   */
 typedef struct tz_search tz_search; /* opaque: BatchedMCTS<B, Game<N,HALF_KOMI>> on one GPU   */
 
-/* architectures (takzero/src/network/{net4_simhash,net5,net6_simhash,net4_lcghash,net4_ensemble}.rs) */
+/* architectures (takzero/src/network/{net4_simhash,net5,net6_simhash,net4_lcghash,net4_ensemble,net4_rnd}.rs) */
 #define TZ_ARCH_NET4_SIMHASH 4
 #define TZ_ARCH_NET5 5
 #define TZ_ARCH_NET6_SIMHASH 6
@@ -101,6 +101,11 @@ typedef struct tz_search tz_search; /* opaque: BatchedMCTS<B, Game<N,HALF_KOMI>>
  * variance of their values (net4_ensemble.rs:146-171, 225-233).  4x4 only; no set of seen positions, no RND. */
 #define TZ_ARCH_NET4_ENSEMBLE 24
 #define TZ_ENSEMBLE_SIZE 16
+/* the trunk and heads of net4_simhash plus two conv towers, `rnd_predictor.*` and `rnd_target.*` (LayerNorm([28,4,4]), conv 28->32,
+ * four 32-filter residual blocks, a last conv + BatchNorm, 512 outputs), and the `min` / `max` of their normalisation; the local
+ * uncertainty is clamp((sum_512 (predictor - target)^2 - min) / (max - min), 0, 1) * 4 (net4_rnd.rs:126-166, 210-230).  4x4 only; no
+ * set of seen positions; the predictor is not trained here (tz_trainer_rnd_enable stays net5's). */
+#define TZ_ARCH_NET4_RND 34
 /* test architecture: same graph as net5 on any board size with configurable depth, no RND/hash */
 #define TZ_ARCH_TEST 100
 
@@ -202,6 +207,12 @@ int tz_net_forward_raw(tz_net* net, int batch, const tz_state* states, float* po
 /* EnsembleNetwork::forward_core_and_ensemble(xs, false) (net4_ensemble.rs:157-171): the sixteen head values of every position,
  * out[batch][16].  TZ_EINVAL unless the net is TZ_ARCH_NET4_ENSEMBLE. */
 int tz_net_ensemble_values(tz_net* net, int batch, const tz_state* states, float* out);
+
+/* RndNetwork::forward_rnd(xs, false) (net4_rnd.rs:210-223): raw_out[batch] = sum_512 (predictor - target)^2, the values the
+ * variance of tz_net_eval is made of (variance = clamp(max(e^ube, clamp((raw - min) / (max - min), 0, 1) * 4), 0, 4)) and what
+ * update_rnd_normalization is fed with.  The same bits for a position wherever it sits in a batch, at every batch size and in every
+ * precision but TZ_PREC_F32.  TZ_EINVAL unless the net is TZ_ARCH_NET4_RND. */
+int tz_net_rnd_raw(tz_net* net, int batch, const tz_state* states, float* raw_out);
 
 /* Hash nets (net4_simhash / net6_simhash / net4_lcghash): HashNetwork::get_indices / update_counts
  * (net6_simhash.rs:202-243, net4_lcghash.rs:202-249) and the bitvec.bin file that accompanies a model (net6_simhash.rs:152-190). */
@@ -577,6 +588,8 @@ int tz_debug_tower_bench(tz_net* net, int variant, int positions, int iters, flo
 /* Diagnostic: average ms per launch of a hash net's index-plus-lookup kernel (simhash_state_kernel / lcghash_state_kernel) on
  * `batch` positions, between two events around `iters` launches after two warm-up launches. */
 int tz_debug_hash_bench(tz_net* net, int batch, const tz_state* states, int iters, float* ms_out);
+/* the same for the tower kernel of TZ_ARCH_NET4_RND (both towers and the variance rule): milliseconds per launch over `batch` positions */
+int tz_debug_rnd4_bench(tz_net* net, int batch, const tz_state* states, int iters, float* ms_out);
 /* Diagnostic (builds with --ablations, TZ_NET_ABL=8): in-kernel shader clock of the last stamped launch of the net kernel
  * (median over workgroups of delta s_memtime / delta s_memrealtime x 100 MHz) and the median duration of its tower part. */
 int tz_debug_net_clock(tz_net* net, double* mhz_out, double* tower_us_out);

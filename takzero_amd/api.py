@@ -14,7 +14,7 @@ import numpy as np
 from . import _lib
 from ._lib import ROOT_INFO_DTYPE, STATE_DTYPE, TakzeroError, check
 
-ARCH_NET4_SIMHASH, ARCH_NET5, ARCH_NET6_SIMHASH, ARCH_NET4_LCGHASH, ARCH_NET4_ENSEMBLE, ARCH_TEST = 4, 5, 6, 14, 24, 100
+ARCH_NET4_SIMHASH, ARCH_NET5, ARCH_NET6_SIMHASH, ARCH_NET4_LCGHASH, ARCH_NET4_ENSEMBLE, ARCH_NET4_RND, ARCH_TEST = 4, 5, 6, 14, 24, 34, 100
 ENSEMBLE_SIZE = 16
 PREC_BF16, PREC_F32, PREC_F16, PREC_F16X2, PREC_F16C8, PREC_F16C6 = 0, 1, 2, 3, 4, 5
 # Arithmetic of the trunk.  fp16 storage with fp32 accumulation (PREC_F16) is the throughput default: its logits are within
@@ -106,7 +106,7 @@ class Net:
         check(self.lib.tz_net_create(n, arch, device, precision, blocks, C.byref(h)))
         self.h = h
         self.arch, self.precision, self.blocks, self.device = arch, precision, blocks, device
-        self.n = {ARCH_NET5: 5, ARCH_NET4_SIMHASH: 4, ARCH_NET6_SIMHASH: 6, ARCH_NET4_LCGHASH: 4, ARCH_NET4_ENSEMBLE: 4}.get(arch, n)
+        self.n = {ARCH_NET5: 5, ARCH_NET4_SIMHASH: 4, ARCH_NET6_SIMHASH: 6, ARCH_NET4_LCGHASH: 4, ARCH_NET4_ENSEMBLE: 4, ARCH_NET4_RND: 4}.get(arch, n)
 
     def close(self):
         if getattr(self, "h", None):
@@ -209,6 +209,13 @@ class Net:
         st = _states(env_batch)
         out = np.zeros((len(st), ENSEMBLE_SIZE), np.float32)
         check(self.lib.tz_net_ensemble_values(self.h, len(st), st.ctypes.data, out.ctypes.data))
+        return out
+
+    def rnd_raw(self, env_batch):
+        """RndNetwork::forward_rnd(xs, false), net4_rnd.rs:210-223: sum_512 (predictor - target)^2 per position, [B]."""
+        st = _states(env_batch)
+        out = np.zeros(len(st), np.float32)
+        check(self.lib.tz_net_rnd_raw(self.h, len(st), st.ctypes.data, out.ctypes.data))
         return out
 
     def hash_indices(self, env_batch, update=False):

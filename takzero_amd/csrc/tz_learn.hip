@@ -1548,6 +1548,7 @@ int tz_trainer_create(int board_n, int arch, int device_id, int blocks, int batc
     if (arch == TZ_ARCH_NET6_SIMHASH && board_n != 6) return tz_fail(TZ_EINVAL, "tz_trainer_create: net6_simhash is 6x6");
     if (arch == TZ_ARCH_NET4_LCGHASH && board_n != 4) return tz_fail(TZ_EINVAL, "tz_trainer_create: net4_lcghash is 4x4");
     if (arch == TZ_ARCH_NET4_ENSEMBLE && board_n != 4) return tz_fail(TZ_EINVAL, "tz_trainer_create: net4_ensemble is 4x4");
+    if (arch == TZ_ARCH_NET4_RND && board_n != 4) return tz_fail(TZ_EINVAL, "tz_trainer_create: net4_rnd is 4x4");   // its towers, min and max are carried
     if (batch <= 0 || batch % 64) return tz_fail(TZ_EINVAL, "tz_trainer_create: batch must be a positive multiple of 64");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev)

@@ -21,6 +21,7 @@ struct tz_net {
     int n = 0, nn = 0, arch = 0, device = 0, precision = 0, blocks = 0;
     int cin = 0, cin_pad = 0, pol_ch = 0, pol_stride = 0, ppt = 0;
     bool loaded = false, has_rnd = false, has_hash = false, has_ens = false;
+    bool has_rnd_tower = false;   // TZ_ARCH_NET4_RND: the two conv towers (tz_nn_rnd4.hip); has_rnd is net5's MLP
     TensorStore store;         // host copy of the VarStore (fp32, `.a.` / `.b.` names): tz_net_save / clone / load_partial
     uint64_t capture_gen = 0;  // tz_net_invalidate_captures: bumped whenever something a captured simulation names is replaced
     ConvW conv_in, policy;
@@ -38,6 +39,10 @@ struct tz_net {
     float* simhash = nullptr;    // [in_size][32] fp32, reference order (c*nn + px); TZ_ARCH_NET4_LCGHASH: lcghash_init, [in_size] in that order
     uint32_t* bitset = nullptr;  // 2^32 bits, allocated for hash archs
     float* ens_w = nullptr;      // TZ_ARCH_NET4_ENSEMBLE: [conv w [256][16], linear w [16][nn], conv bias [16], linear bias [16]] (ensemble_heads_kernel)
+    // TZ_ARCH_NET4_RND (tz_nn_rnd4.h): the towers' fp16 fragments (every precision but f32) or fp32 weights, folded biases, LayerNorm
+    // affines; rnd_min / rnd_max above hold `min` / `max`; a forward leaves raw in `aux`
+    uint16_t* rnd4_w = nullptr;
+    float *rnd4_wf = nullptr, *rnd4_bias = nullptr, *rnd4_ln = nullptr;
     // work buffers, sized for max_batch positions
     int max_batch = 0;
     void *act_a = nullptr, *act_b = nullptr, *act_c = nullptr;  // [max_batch*nn][256] bf16 or f32

@@ -20,6 +20,7 @@
 #include "tz_math.h"
 #include <type_traits>
 #include "tz_ot.h"
+#include "tz_nn_rnd4.h"
 
 #include <algorithm>
 #include <cmath>
@@ -3202,6 +3203,8 @@ struct NetWeights {  // everything tz_net_load_weights replaces, so a failed loa
     float rnd_min = 0.f, rnd_max = 1.f;
     float* simhash = nullptr;
     float* ens_w = nullptr;
+    uint16_t* rnd4_w = nullptr;   // TZ_ARCH_NET4_RND: see tz_net
+    float *rnd4_wf = nullptr, *rnd4_bias = nullptr, *rnd4_ln = nullptr;
 };
 
 void free_weights(NetWeights& w) {
@@ -3233,6 +3236,12 @@ void free_weights(NetWeights& w) {
     w.simhash = nullptr;
     if (w.ens_w) (void)hipFree(w.ens_w);
     w.ens_w = nullptr;
+    if (w.rnd4_w) (void)hipFree(w.rnd4_w);
+    if (w.rnd4_wf) (void)hipFree(w.rnd4_wf);
+    if (w.rnd4_bias) (void)hipFree(w.rnd4_bias);
+    if (w.rnd4_ln) (void)hipFree(w.rnd4_ln);
+    w.rnd4_w = nullptr;
+    w.rnd4_wf = w.rnd4_bias = w.rnd4_ln = nullptr;
 }
 
 int build_weights(tz_net* net, const TensorMap& m, NetWeights& W) {
@@ -3399,6 +3408,46 @@ int build_weights(tz_net* net, const TensorMap& m, NetWeights& W) {
             lw[ENS_HEADS * ENS_NN + ENS_HEADS + h] = t1[0];
         }
         if ((rc = upload(ew, &W.ens_w))) return rc;
+    }
+    if (net->has_rnd_tower) {   // rnd_predictor and rnd_target (net4_rnd.rs:126-166, 181-186): BatchNorm folded as the trunk's is
+        std::vector<uint16_t> hw(prec != TZ_PREC_F32 ? (size_t)2 * R4_LAYERS * R4_LAYER_HALVES : 0);
+        std::vector<float> fw(prec == TZ_PREC_F32 ? (size_t)2 * R4_LAYERS * 9 * R4_CH * R4_CH : 0);
+        std::vector<float> fb((size_t)2 * R4_LAYERS * R4_CH), ln((size_t)2 * 2 * R4_IN);
+        const char* towers[2] = {"rnd_predictor", "rnd_target"};
+        for (int t = 0; t < 2; t++) {
+            const std::string tp = towers[t];
+            if ((rc = get_tensor(m, tp + ".layer_norm.weight", R4_IN, w))) return rc;
+            memcpy(&ln[(size_t)t * 2 * R4_IN], w.data(), R4_IN * sizeof(float));
+            if ((rc = get_tensor(m, tp + ".layer_norm.bias", R4_IN, w))) return rc;
+            memcpy(&ln[(size_t)(t * 2 + 1) * R4_IN], w.data(), R4_IN * sizeof(float));
+            for (int l = 0; l < R4_LAYERS; l++) {
+                const std::string p = l == 0 ? tp + ".input_conv2d" : l == R4_LAYERS - 1 ? tp + ".last_small_block.conv2d"
+                                             : tp + ".res_block_" + std::to_string((l - 1) / 2) + ((l - 1) & 1 ? ".b" : ".a") + ".conv2d";
+                const std::string q = l == 0 ? tp + ".batch_norm" : p.substr(0, p.size() - 6) + "batch_norm";
+                const int ci_n = l == 0 ? R4_CIN : R4_CH;
+                if ((rc = get_tensor(m, p + ".weight", (size_t)R4_CH * ci_n * 9, w))) return rc;
+                if ((rc = bn_fold(m, q, R4_CH, scale, bias))) return rc;
+                const size_t li = (size_t)t * R4_LAYERS + l;
+                memcpy(&fb[li * R4_CH], bias.data(), R4_CH * sizeof(float));
+                for (int tap = 0; tap < 9; tap++)
+                    for (int ci = 0; ci < R4_CH; ci++)
+                        for (int co = 0; co < R4_CH; co++) {
+                            const float v = ci < ci_n ? w[((size_t)co * ci_n + ci) * 9 + tap] * scale[co] : 0.f;
+                            if (prec == TZ_PREC_F32) fw[((li * 9 + tap) * R4_CH + ci) * R4_CH + co] = v;
+                            // B fragment of v_mfma_f32_16x16x32_f16: lane holds B[k = 8 (lane >> 4) + j][column lane & 15]
+                            else hw[li * R4_LAYER_HALVES + (((size_t)tap * 2 + co / 16) * 64 + (ci / 8) * 16 + co % 16) * 8 + ci % 8] = f2h(v);
+                        }
+            }
+        }
+        if (prec == TZ_PREC_F32) rc = upload(fw, &W.rnd4_wf);
+        else rc = upload(hw, &W.rnd4_w);
+        if (rc) return rc;
+        if ((rc = upload(fb, &W.rnd4_bias))) return rc;
+        if ((rc = upload(ln, &W.rnd4_ln))) return rc;
+        if ((rc = get_tensor(m, "min", 1, w))) return rc;
+        W.rnd_min = w[0];
+        if ((rc = get_tensor(m, "max", 1, w))) return rc;
+        W.rnd_max = w[0];
     }
     return TZ_OK;
 }
@@ -3655,8 +3704,8 @@ int net_small_p(int max_positions) {
     return max_positions <= 256 ? 1 : max_positions <= 512 ? 2 : max_positions <= 1024 ? 4 : 0;
 }
 
-#if defined(TZ_NN_C6_TU)
-}  // namespace   (tz_nn_c6.hip goes on from here)
+#if defined(TZ_NN_C6_TU) || defined(TZ_NN_RND4_TU)
+}  // namespace   (tz_nn_c6.hip and tz_nn_rnd4.hip go on from here)
 #elif defined(TZ_NN_SPLIT_TU)
 }  // namespace
 
@@ -4091,6 +4140,10 @@ int tz_net_forward_device(tz_net* net, const tz_state* states, const int32_t* gi
         else if (prec_is_f16(net->precision))
             ensemble_heads_kernel<_Float16><<<max_positions, 256, 0, st>>>((const _Float16*)last, net->ens_w, count_dev, count_host, net->ens_values, net->aux, net->ube, net->variance);
         else ensemble_heads_kernel<__bf16><<<max_positions, 256, 0, st>>>((const __bf16*)last, net->ens_w, count_dev, count_host, net->ens_values, net->aux, net->ube, net->variance);
+    } else if (net->has_rnd_tower) {   // both towers and the variance rule in one launch behind the trunk (tz_nn_rnd4.hip); raw stays in aux
+        if ((rc = tz_nn_launch_rnd4(!bf, states, gidx, count_dev, count_host, max_positions, net->rnd4_w, net->rnd4_wf, net->rnd4_bias,
+                                    net->rnd4_ln, net->ube, net->rnd_min, net->rnd_max, net->aux, net->variance, st)))
+            return rc;
     } else if (net->has_rnd) {
         const int in_size = net->cin * nn, in_pad = (in_size + 31) / 32 * 32;
         float* outs[2] = {net->rnd_out, net->rnd_out + (size_t)net->max_batch * 512};
@@ -4147,7 +4200,7 @@ int tz_net_create(int board_n, int arch, int device_id, int precision, int block
     if (arch == TZ_ARCH_NET5) n = 5;
     else if (arch == TZ_ARCH_NET4_SIMHASH) n = 4;
     else if (arch == TZ_ARCH_NET6_SIMHASH) n = 6;
-    else if (arch == TZ_ARCH_NET4_LCGHASH || arch == TZ_ARCH_NET4_ENSEMBLE) n = 4;
+    else if (arch == TZ_ARCH_NET4_LCGHASH || arch == TZ_ARCH_NET4_ENSEMBLE || arch == TZ_ARCH_NET4_RND) n = 4;
     else if (arch != TZ_ARCH_TEST) return tz_fail(TZ_EINVAL, "tz_net_create: unknown architecture");
     if (board_n && board_n != n) return tz_fail(TZ_EINVAL, "tz_net_create: board size does not match the architecture");
     if (n < 3 || n > 6) return tz_fail(TZ_EINVAL, "tz_net_create: board size must be 3..6");
@@ -4175,6 +4228,7 @@ int tz_net_create(int board_n, int arch, int device_id, int precision, int block
     net->has_rnd = arch == TZ_ARCH_NET5;
     net->has_hash = arch == TZ_ARCH_NET4_SIMHASH || arch == TZ_ARCH_NET6_SIMHASH || arch == TZ_ARCH_NET4_LCGHASH;
     net->has_ens = arch == TZ_ARCH_NET4_ENSEMBLE;
+    net->has_rnd_tower = arch == TZ_ARCH_NET4_RND;   // has_rnd is net5's MLP and stays false
     if (hipStreamCreate(&net->stream) != hipSuccess) {
         delete net;
         return tz_fail(TZ_EDEVICE, "tz_net_create: hipStreamCreate failed");
@@ -4247,6 +4301,14 @@ static int net_commit_pending(tz_net* net, tz_pending_weights* p) {
     old.simhash = net->simhash;
     old.ens_w = net->ens_w;
     net->ens_w = W.ens_w;
+    old.rnd4_w = net->rnd4_w;
+    old.rnd4_wf = net->rnd4_wf;
+    old.rnd4_bias = net->rnd4_bias;
+    old.rnd4_ln = net->rnd4_ln;
+    net->rnd4_w = W.rnd4_w;
+    net->rnd4_wf = W.rnd4_wf;
+    net->rnd4_bias = W.rnd4_bias;
+    net->rnd4_ln = W.rnd4_ln;
     net->conv_in = W.conv_in;
     net->policy = W.policy;
     net->res = W.res;
@@ -4513,6 +4575,29 @@ int tz_net_init_random(tz_net* net, uint64_t seed) {
         const std::string p = "ensemble head " + std::to_string(h);
         init_conv(st, seed, p + ".conv2d", 1, FILTERS, 1, true);
         init_linear(st, seed, p + ".linear", 1, nn);
+    }
+    if (net->has_rnd_tower) {   // net4_rnd.rs:126-166, 181-186: LayerNorm weight 1 / bias 0, the trunk's initialisers for conv and BatchNorm
+        for (const char* r : {"rnd_predictor", "rnd_target"}) {
+            const std::string tp = r;
+            HostTensor one;
+            one.dims = {(uint32_t)R4_CIN, 4, 4};
+            one.data.assign(R4_IN, 1.f);
+            st[tp + ".layer_norm.weight"] = one;
+            one.data.assign(R4_IN, 0.f);
+            st[tp + ".layer_norm.bias"] = one;
+            init_conv(st, seed, tp + ".input_conv2d", R4_CH, R4_CIN, 3, false);
+            init_bn(st, seed, tp + ".batch_norm", R4_CH);
+            for (int b = 0; b < (R4_LAYERS - 2) / 2; b++)
+                for (const char* half : {".a", ".b"}) {
+                    const std::string p = tp + ".res_block_" + std::to_string(b) + half;
+                    init_conv(st, seed, p + ".conv2d", R4_CH, R4_CH, 3, false);
+                    init_bn(st, seed, p + ".batch_norm", R4_CH);
+                }
+            init_conv(st, seed, tp + ".last_small_block.conv2d", R4_CH, R4_CH, 3, false);
+            init_bn(st, seed, tp + ".last_small_block.batch_norm", R4_CH);
+        }
+        init_const(st, "min", 1, 0.f);
+        init_const(st, "max", 1, 1.f);
     }
     if (net->arch == TZ_ARCH_NET4_LCGHASH) {   // root.uniform("lcghash_init", [C, N, N], -100, 100), net4_lcghash.rs:131-136
         init_uniform(st, seed, "lcghash_init", {cin, (uint32_t)net->n, (uint32_t)net->n}, -100.0, 100.0);
@@ -4826,6 +4911,10 @@ int tz_net_destroy(tz_net* net) {
     }
     old.simhash = net->simhash;
     old.ens_w = net->ens_w;
+    old.rnd4_w = net->rnd4_w;
+    old.rnd4_wf = net->rnd4_wf;
+    old.rnd4_bias = net->rnd4_bias;
+    old.rnd4_ln = net->rnd4_ln;
     free_weights(old);
     void* bufs[] = {net->act_a, net->act_b, net->act_c, net->planes, net->policy_out, net->value, net->ube,
                     net->variance, net->aux, net->rnd_in, net->rnd_h1, net->rnd_h2, net->rnd_out, net->bitset, net->seeds, net->xch, net->xch_count,
@@ -5011,6 +5100,39 @@ int tz_debug_hash_bench(tz_net* net, int batch, const tz_state* states, int iter
     return TZ_OK;
 }
 
+// the tower kernel of TZ_ARCH_NET4_RND alone (both towers and the variance rule, on the UBE of the net's last forward) between two events
+int tz_debug_rnd4_bench(tz_net* net, int batch, const tz_state* states, int iters, float* ms_out) {
+    if (!net || !states || !ms_out || batch <= 0 || iters <= 0) return tz_fail(TZ_EINVAL, "tz_debug_rnd4_bench: bad argument");
+    if (!net->has_rnd_tower || !net->loaded) return tz_fail(TZ_ESTATE, "tz_debug_rnd4_bench: not a loaded TZ_ARCH_NET4_RND network");
+    tz_state* dstates = nullptr;
+    int rc = net_upload_states(net, batch, states, &dstates);
+    if (rc) return rc;
+    hipStream_t st = net->stream;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    float ms = 0.f;
+    hipError_t e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    if (e == hipSuccess) e = hipMemsetAsync(net->ube, 0, (size_t)batch * sizeof(float), st);
+    auto launch = [&]() {
+        return tz_nn_launch_rnd4(net->precision == TZ_PREC_F32, dstates, nullptr, nullptr, batch, batch, net->rnd4_w, net->rnd4_wf, net->rnd4_bias,
+                                 net->rnd4_ln, net->ube, net->rnd_min, net->rnd_max, net->aux, net->variance, st);
+    };
+    for (int i = 0; i < 2 && e == hipSuccess && !rc; i++) rc = launch();
+    if (e == hipSuccess && !rc) e = hipEventRecord(e0, st);
+    for (int i = 0; i < iters && e == hipSuccess && !rc; i++) rc = launch();
+    if (e == hipSuccess && !rc) e = hipEventRecord(e1, st);
+    if (e == hipSuccess && !rc) e = hipEventSynchronize(e1);
+    if (e == hipSuccess && !rc) e = hipEventElapsedTime(&ms, e0, e1);
+    if (e == hipSuccess && !rc) e = hipGetLastError();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    (void)hipFree(dstates);
+    if (rc) return rc;
+    if (e != hipSuccess) return tz_fail(TZ_EDEVICE, std::string("tz_debug_rnd4_bench: ") + hipGetErrorString(e));
+    *ms_out = ms / iters;
+    return TZ_OK;
+}
+
 // bitvec.bin: the raw words of the reference's BitBox<usize, Lsb0> (2^32 bits = 512 MiB), net6_simhash.rs:152-190
 int tz_net_load_bitset(tz_net* net, const char* path) {
     if (!net || !path) return tz_fail(TZ_EINVAL, "tz_net_load_bitset: null argument");
@@ -5113,6 +5235,29 @@ int tz_net_ensemble_values(tz_net* net, int batch, const tz_state* states, float
     (void)hipFree(dstates);
     if (rc) return rc;
     if (e != hipSuccess) return tz_fail(TZ_EDEVICE, std::string("tz_net_ensemble_values: ") + hipGetErrorString(e));
+    return TZ_OK;
+}
+
+// RndNetwork::forward_rnd(xs, false) (net4_rnd.rs:210-223): sum_512 (predictor - target)^2 of every position, as the tower kernel left it
+int tz_net_rnd_raw(tz_net* net, int batch, const tz_state* states, float* raw_out) {
+    if (!net || !states || !raw_out || batch <= 0) return tz_fail(TZ_EINVAL, "tz_net_rnd_raw: bad argument");
+    if (!net->has_rnd_tower) return tz_fail(TZ_EINVAL, "tz_net_rnd_raw: not a TZ_ARCH_NET4_RND network");
+    for (int b = 0; b < batch; b++)
+        if (states[b].n != net->n) return tz_fail(TZ_EINVAL, "tz_net_rnd_raw: state board size does not match the network");
+    tz_state* dstates = nullptr;
+    int rc = net_upload_states(net, batch, states, &dstates);
+    if (rc) return rc;
+    hipStream_t st = net->stream;
+    NetOut o;
+    rc = tz_net_forward_device(net, dstates, nullptr, nullptr, batch, batch, st, &o);
+    hipError_t e = hipSuccess;
+    if (!rc) {
+        e = hipMemcpyAsync(raw_out, net->aux, (size_t)batch * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    }
+    (void)hipFree(dstates);
+    if (rc) return rc;
+    if (e != hipSuccess) return tz_fail(TZ_EDEVICE, std::string("tz_net_rnd_raw: ") + hipGetErrorString(e));
     return TZ_OK;
 }
 

@@ -621,14 +621,18 @@ int ot_canonical_names(const NamedTensors& in, TensorStore& out) {
                 dup = true;
             }
         }
-        const std::string pre = "core.res_block_";
-        if (!base.compare(0, pre.size(), pre)) {
+        bool block = false;   // the trunk's blocks and those of net4_rnd's two towers (net4_rnd.rs:153-159)
+        for (const char* pre_c : {"core.res_block_", "rnd_predictor.res_block_", "rnd_target.res_block_"}) {
+            const std::string pre = pre_c;
+            if (base.compare(0, pre.size(), pre)) continue;
             const size_t dot = base.find('.', pre.size());
             if (dot != std::string::npos) {
                 out[base.substr(0, dot) + (dup ? ".b." : ".a.") + base.substr(dot + 1)] = kv.second;
-                continue;
+                block = true;
             }
+            break;
         }
+        if (block) continue;
         if (dup) return tz_fail(TZ_EPARSE, "model archive: duplicated variable outside a residual block: " + kv.first);
         out[base] = kv.second;
     }
@@ -636,7 +640,7 @@ int ot_canonical_names(const NamedTensors& in, TensorStore& out) {
 }
 
 void ot_tch_names(const TensorStore& in, NamedTensors& out) {
-    // Creation order of Net::new (net5.rs:152-170, net6_simhash.rs:122-141, net4_ensemble.rs:107-131): core (input conv, batch norm, blocks), policy,
+    // Creation order of Net::new (net5.rs:152-170, net6_simhash.rs:122-141, net4_ensemble.rs:107-131, net4_rnd.rs:169-189): core (input conv, batch norm, blocks), policy,
     // value, ube, then the uncertainty side nets.  A path that already exists gets `__<variables registered so far>`
     // (tch nn::Path::add).  Inside nn::batch_norm, tch creates weight and bias (the `affine` pair) before running_mean and
     // running_var; TZ_TCH_BN_ORDER=stats_first gives the older order.  Neither is pinned by a file of the reference (none is
@@ -680,7 +684,30 @@ void ot_tch_names(const TensorStore& in, NamedTensors& out) {
                           "simhash_matrix", "lcghash_init"};
     std::map<std::string, bool> done;
     for (auto& kv : out) done[kv.first] = true;
+    auto rnd_tower = [&](const std::string& p) {   // net4_rnd.rs:126-166: LayerNorm, input conv + BatchNorm, blocks, last SmallBlock
+        if (!in.count(p + ".layer_norm.weight")) return;
+        add(p + ".layer_norm.weight", p + ".layer_norm.weight");
+        add(p + ".layer_norm.bias", p + ".layer_norm.bias");
+        add(p + ".input_conv2d.weight", p + ".input_conv2d.weight");
+        bn(p + ".batch_norm", p + ".batch_norm");
+        for (int blk = 0;; blk++) {
+            const std::string q = p + ".res_block_" + std::to_string(blk);
+            if (!in.count(q + ".a.conv2d.weight")) break;
+            for (const char* half : {".a", ".b"}) {
+                add(q + ".conv2d.weight", q + half + ".conv2d.weight");
+                bn(q + ".batch_norm", q + half + ".batch_norm");
+            }
+        }
+        add(p + ".last_small_block.conv2d.weight", p + ".last_small_block.conv2d.weight");
+        bn(p + ".last_small_block.batch_norm", p + ".last_small_block.batch_norm");
+        for (auto& kv : in)
+            if (!kv.first.compare(0, p.size() + 1, p + ".")) done[kv.first] = true;
+    };
     for (const char* r : rest) {
+        if (!strcmp(r, "min")) {   // the towers come before min and max (net4_rnd.rs:181-186), predictor first
+            rnd_tower("rnd_predictor");
+            if (in.count("rnd_predictor.layer_norm.weight")) rnd_tower("rnd_target");
+        }
         add(r, r);
         done[r] = true;
     }

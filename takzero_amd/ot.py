@@ -22,7 +22,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 WRITER = os.path.join(HERE, "ot_writer")
 
 _SUFFIX = re.compile(r"^(.*)__(\d+)$")
-_BLOCK = re.compile(r"^(core\.res_block_\d+)\.(.+)$")
+_BLOCK = re.compile(r"^((?:core|rnd_predictor|rnd_target)\.res_block_\d+)\.(.+)$")   # net4_rnd.rs:153-159: the towers' blocks too
 
 
 def read_ot_libtorch(path):
@@ -70,7 +70,7 @@ def load_ot_libtorch(path):
 
 def tch_names(tensors):
     """The inverse (what tch would name the variables when it builds the net: creation order of net5.rs /
-    net6_simhash.rs / net4_lcghash.rs / net4_ensemble.rs, duplicates suffixed with the number of variables registered so far).  Used to write test
+    net6_simhash.rs / net4_lcghash.rs / net4_ensemble.rs / net4_rnd.rs, duplicates suffixed with the number of variables registered so far).  Used to write test
     archives; the reader above does not depend on the exact numbers."""
     out, count = [], 0
     seen = set()
@@ -99,8 +99,28 @@ def tch_names(tensors):
             add("core.res_block_%d.conv2d.weight" % b, "core.res_block_%d.%s.conv2d.weight" % (b, half))
             bn("core.res_block_%d.batch_norm" % b, "core.res_block_%d.%s.batch_norm" % (b, half))
         b += 1
-    rest = [k for k in tensors if not k.startswith("core.")]
+    # net4_rnd's towers (net5's RND MLP is `rnd_target.*` too, and stays with the rest)
+    towers = ("rnd_predictor.", "rnd_target.") if "rnd_predictor.layer_norm.weight" in tensors else ()
+    last = ("min", "max") if towers else ()
+    rest = [k for k in tensors if not k.startswith(("core.",) + towers) and k not in last]
     for k in rest:
+        add(k, k)
+    for p in towers:   # net4_rnd.rs:126-166, 181-186: after ube, predictor first, then min and max
+        if p + "layer_norm.weight" not in tensors:
+            continue
+        add(p + "layer_norm.weight", p + "layer_norm.weight")
+        add(p + "layer_norm.bias", p + "layer_norm.bias")
+        add(p + "input_conv2d.weight", p + "input_conv2d.weight")
+        bn(p + "batch_norm", p + "batch_norm")
+        b = 0
+        while "%sres_block_%d.a.conv2d.weight" % (p, b) in tensors:
+            for half in "ab":
+                add("%sres_block_%d.conv2d.weight" % (p, b), "%sres_block_%d.%s.conv2d.weight" % (p, b, half))
+                bn("%sres_block_%d.batch_norm" % (p, b), "%sres_block_%d.%s.batch_norm" % (p, b, half))
+            b += 1
+        add(p + "last_small_block.conv2d.weight", p + "last_small_block.conv2d.weight")
+        bn(p + "last_small_block.batch_norm", p + "last_small_block.batch_norm")
+    for k in last:
         add(k, k)
     return out
 

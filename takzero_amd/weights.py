@@ -11,7 +11,7 @@ reference creates under one path, residual.rs:50-55) are spelled `.a.` and `.b.`
     u16 name length, name (utf-8), u8 ndim, u32 dims[ndim], f32 data (little endian, C order)
 
 Architectures: net5 (takzero/src/network/net5.rs:44-148), net4_simhash /
-net6_simhash (net6_simhash.rs:43-141), net4_lcghash (net4_lcghash.rs:39-140), net4_ensemble (net4_ensemble.rs:39-131).  `init_weights` follows tch's defaults as the reference
+net6_simhash (net6_simhash.rs:43-141), net4_lcghash (net4_lcghash.rs:39-140), net4_ensemble (net4_ensemble.rs:39-131), net4_rnd (net4_rnd.rs:48-186).  `init_weights` follows tch's defaults as the reference
 relies on them: conv/linear weights Kaiming-uniform(a=sqrt 5), biases U(+-1/sqrt(fan_in)),
 BatchNorm weight U(0,1), bias 0, running stats 0/1, RND min 0 / max 1 (net5.rs:166-168).
 """
@@ -25,6 +25,8 @@ ARCH_NET6_SIMHASH = 6
 ARCH_NET4_LCGHASH = 14
 ARCH_NET4_ENSEMBLE = 24
 ENSEMBLE_SIZE = 16
+ARCH_NET4_RND = 34
+RND4_FILTERS, RND4_BLOCKS = 32, 4
 ARCH_TEST = 100
 FILTERS = 256
 HASH_BITS = 32
@@ -41,11 +43,11 @@ def output_channels(n):
 
 
 def arch_blocks(arch, blocks=0):
-    return {ARCH_NET5: 20, ARCH_NET4_SIMHASH: 16, ARCH_NET6_SIMHASH: 16, ARCH_NET4_LCGHASH: 16, ARCH_NET4_ENSEMBLE: 16}.get(arch, blocks)
+    return {ARCH_NET5: 20, ARCH_NET4_SIMHASH: 16, ARCH_NET6_SIMHASH: 16, ARCH_NET4_LCGHASH: 16, ARCH_NET4_ENSEMBLE: 16, ARCH_NET4_RND: 16}.get(arch, blocks)
 
 
 def arch_board(arch, n=0):
-    return {ARCH_NET5: 5, ARCH_NET4_SIMHASH: 4, ARCH_NET6_SIMHASH: 6, ARCH_NET4_LCGHASH: 4, ARCH_NET4_ENSEMBLE: 4}.get(arch, n)
+    return {ARCH_NET5: 5, ARCH_NET4_SIMHASH: 4, ARCH_NET6_SIMHASH: 6, ARCH_NET4_LCGHASH: 4, ARCH_NET4_ENSEMBLE: 4, ARCH_NET4_RND: 4}.get(arch, n)
 
 
 def save_tzw(path, tensors):
@@ -142,6 +144,22 @@ def init_weights(arch, n=0, blocks=0, seed=123, trained_stats=False):
         for i in range(ENSEMBLE_SIZE):
             _conv(rng, t, "ensemble head %d.conv2d" % i, 1, FILTERS, 1, True)
             _linear(rng, t, "ensemble head %d.linear" % i, 1, nn)
+    if arch == ARCH_NET4_RND:
+        # rnd_predictor, then rnd_target, then min / max (net4_rnd.rs:126-166, 181-186): LayerNorm weight 1 / bias 0 (tch's default)
+        for net in ("rnd_predictor", "rnd_target"):
+            t[net + ".layer_norm.weight"] = np.ones((cin, n, n), np.float32)
+            t[net + ".layer_norm.bias"] = np.zeros((cin, n, n), np.float32)
+            _conv(rng, t, net + ".input_conv2d", RND4_FILTERS, cin, 3, False)
+            _bn(rng, t, net + ".batch_norm", RND4_FILTERS, trained_stats)
+            for b in range(RND4_BLOCKS):
+                for half in "ab":
+                    p = "%s.res_block_%d.%s" % (net, b, half)
+                    _conv(rng, t, p + ".conv2d", RND4_FILTERS, RND4_FILTERS, 3, False)
+                    _bn(rng, t, p + ".batch_norm", RND4_FILTERS, trained_stats)
+            _conv(rng, t, net + ".last_small_block.conv2d", RND4_FILTERS, RND4_FILTERS, 3, False)
+            _bn(rng, t, net + ".last_small_block.batch_norm", RND4_FILTERS, trained_stats)
+        t["min"] = np.zeros(1, np.float32)
+        t["max"] = np.ones(1, np.float32)
     if arch == ARCH_NET5:
         for net in ("rnd_learning", "rnd_target"):
             _linear(rng, t, net + ".input_linear", RND_HIDDEN, cin * nn)
