@@ -6,7 +6,7 @@
 //
 //   g++ -std=c++17 -O2 examples/learn_cli.cpp -Iinclude -Ltakzero_amd -ltakzero_hip -Wl,-rpath,$PWD/takzero_amd -o learn_cli
 //   ./learn_cli --directory DIR --arch 5 --steps 100000
-// --train-rnd (net5): the steps of the main loop also train the RND predictor (loss_rnd, learn/src/main.rs:404-405) and min / max are
+// --train-rnd (net5, net4_rnd): the steps of the main loop also train the RND predictor (loss_rnd, learn/src/main.rs:404-405) and min / max are
 // calibrated (update_rnd, :415-416) on reference positions made from --seed before every model file, and every
 // --rnd-calibrate-every steps when that is given.
 #include <dirent.h>
@@ -65,7 +65,7 @@ static const char* USAGE =
     "  --arch 4|5|6|14|24|34|100|net4_simhash|net5|net6_simhash|net4_lcghash|net4_ensemble|net4_rnd|test  --n N  --blocks K  --batch B  --steps S  --seed X\n"
     "  --pre-training-steps S  --initial-targets T  --steps-before-reanalyze S  --min-selfplay T  --min-reanalyze T\n"
     "  --steps-per-save S  --steps-per-checkpoint S  --read-interval SEC  --sleep SEC  --wait-limit SEC  --verbose\n"
-    "  --train-rnd               net5 only: train the RND predictor in every step of the main loop and calibrate min / max\n"
+    "  --train-rnd               net5 and net4_rnd only: train the RND predictor in every step of the main loop and calibrate min / max\n"
     "                            before every model file (reference positions from --seed)\n"
     "  --rnd-calibrate-every N   also calibrate every N steps (default 0: only before model files)\n";
 
@@ -111,8 +111,8 @@ int main(int argc, char** argv) {
         fputs(USAGE, stderr);
         return 2;
     }
-    if (train_rnd && arch != TZ_ARCH_NET5) {
-        fprintf(stderr, "--train-rnd needs --arch 5: only net5 has RND networks\n");
+    if (train_rnd && arch != TZ_ARCH_NET5 && arch != TZ_ARCH_NET4_RND) {
+        fprintf(stderr, "--train-rnd needs --arch 5 or --arch net4_rnd: only net5 and net4_rnd have RND networks\n");
         return 2;
     }
     if (rnd_calibrate_every < 0) {
@@ -196,7 +196,8 @@ int main(int argc, char** argv) {
         CHECK(tz_learn_rnd_reference(mcts, seed, 256, 4, 256, 120, early.data(), late.data()));
         tz_search_destroy(mcts);
         CHECK(tz_learn_set_rnd(loop, 1, early.data(), 256, late.data(), 256, rnd_calibrate_every));
-        CHECK(tz_trainer_rnd_calibrate(trainer, early.data(), 256, late.data(), 256, 1, nullptr, nullptr));
+        if (arch == TZ_ARCH_NET4_RND) CHECK(tz_trainer_rnd4_calibrate(trainer, early.data(), 256, late.data(), 256, 1, nullptr, nullptr));
+        else CHECK(tz_trainer_rnd_calibrate(trainer, early.data(), 256, late.data(), 256, 1, nullptr, nullptr));
     }
     CHECK(tz_trainer_save(trainer, (directory + "/model_latest.ot").c_str()));
     int64_t model_steps = starting_steps;

@@ -104,7 +104,7 @@ typedef struct tz_search tz_search; /* opaque: BatchedMCTS<B, Game<N,HALF_KOMI>>
 /* the trunk and heads of net4_simhash plus two conv towers, `rnd_predictor.*` and `rnd_target.*` (LayerNorm([28,4,4]), conv 28->32,
  * four 32-filter residual blocks, a last conv + BatchNorm, 512 outputs), and the `min` / `max` of their normalisation; the local
  * uncertainty is clamp((sum_512 (predictor - target)^2 - min) / (max - min), 0, 1) * 4 (net4_rnd.rs:126-166, 210-230).  4x4 only; no
- * set of seen positions; the predictor is not trained here (tz_trainer_rnd_enable stays net5's). */
+ * set of seen positions; tz_trainer_rnd4_enable trains the predictor in the step (tz_trainer_rnd_enable stays net5's). */
 #define TZ_ARCH_NET4_RND 34
 /* test architecture: same graph as net5 on any board size with configurable depth, no RND/hash */
 #define TZ_ARCH_TEST 100
@@ -536,6 +536,45 @@ int tz_trainer_rnd_activation(tz_trainer* t, int which, int layer, float* out, u
 int tz_trainer_rnd_calibrate(tz_trainer* t, const tz_state* early, int n_early, const tz_state* late, int n_late, int apply,
                              float* min_out, float* max_out);
 
+/* ---------- Training net4_rnd's predictor tower in the step (net4_rnd.rs:126-166, 210-223; residual.rs:8-63; learn/src/main.rs:404-405,
+ * 415-416; eee/src/rnd.rs) ----------
+ * Off until asked for: with it never enabled a trainer of this architecture carries the 106 tower variables unchanged and does, bit
+ * for bit, what it did without these calls.
+ * tz_trainer_rnd4_enable: on != 0 switches the distillation step on.  tz_trainer_step then also runs both towers on the batch's planes:
+ * rnd_predictor in training mode (LayerNorm with the population variance, eps 1e-5; BatchNorm with the batch's mean and biased
+ * variance over batch * 16 rows, eps 1e-5), rnd_target in eval mode (its running statistics), takes loss_rnd = mean_b sum_512
+ * (predictor - target)^2 (net4_rnd.rs:210-223 with train = true, main.rs:404) and its gradient through the predictor only.  With
+ * apply_step Adam (the trunk's lr, betas and eps) moves the predictor's 32 trained variables (LayerNorm weight and bias, then ten
+ * times conv weight, BatchNorm weight, BatchNorm bias) with a step count of their own (the feature may be switched on in the middle
+ * of a run), and the predictor's 20 running statistics move with momentum 0.1 and the unbiased variance (tch / torch).  With
+ * apply_step = 0 the losses and gradients are computed and nothing else moves: no weight, no moment and, unlike the trunk's forward,
+ * no running statistic of the tower.  train_ube has no bearing on it; rnd_target.*, min and max never change in a step.  Every sum
+ * across workgroups is added in a fixed order: two runs give the same bits.
+ * While enabled the predictor's 32 trained names answer to tz_trainer_get_tensor / _set_tensor (what 0..3, conv weights as
+ * [co][ci][3][3]) and its 20 running statistics with what = 0; tz_trainer_tensor_count / _info list what they always list.  Save,
+ * to_net, snapshot and get_extras carry the current predictor; a load re-uploads the model's towers.
+ * TZ_EINVAL unless the trainer is TZ_ARCH_NET4_RND; TZ_ESTATE when the loaded variables hold no rnd_predictor.* / rnd_target.* /
+ * min / max. */
+int tz_trainer_rnd4_enable(tz_trainer* t, int on);
+/* loss_rnd (main.rs:404) and forward_rnd(xs, true) (net4_rnd.rs:210-223) [batch] of the last enabled step, computed before that step's
+ * update.  Either pointer may be NULL.  TZ_ESTATE before the first enabled step. */
+int tz_trainer_rnd4_last(tz_trainer* t, float* loss_out, float* raw_out /*[batch]*/);
+/* What the last enabled step left in a tower (net4_rnd.rs:126-166): which 0 = rnd_predictor, 1 = rnd_target.
+ *   layer 0        the LayerNorm output, [batch][28][4][4]
+ *   layer 1..10    the output of conv layer 1..10 (input conv, res_block_0.a, res_block_0.b, .., res_block_3.b, last_small_block) after
+ *                  BatchNorm, the residual add and ReLU (none after layer 10), [batch][16 squares][32 channels]
+ *   layer 11..20   predictor only: the conv output of layer 1..10 before BatchNorm, [batch][16][32]
+ * out_cap in floats.  For tests, like tz_trainer_activation. */
+int tz_trainer_rnd4_activation(tz_trainer* t, int which /*0 predictor, 1 target*/, int layer, float* out, uint64_t out_cap);
+/* update_rnd (learn/src/rnd_normalization.rs:74-78): min of forward_rnd(xs, false) over the early positions, max over the late ones,
+ * both towers in eval mode (the predictor with its current running statistics); any counts >= 1, in chunks of the trainer's batch.
+ * Computed by the inference library's own TZ_PREC_F32 tower on the trainer's current variables folded as a model's are, so the
+ * values are exactly what the saved model returns from tz_net_rnd_raw in that precision.  apply != 0 stores them in the variables
+ * min / max (update_rnd_normalization, net4_rnd.rs:232-237).  min_out / max_out may be NULL.  If !(max > min) the call returns
+ * TZ_ESTATE and, with apply set, leaves the variables alone (as tz_trainer_rnd_calibrate).  TZ_ESTATE also while not enabled. */
+int tz_trainer_rnd4_calibrate(tz_trainer* t, const tz_state* early, int n_early, const tz_state* late, int n_late, int apply,
+                              float* min_out, float* max_out);
+
 /* ---------- learn::main above the step (learn/src/main.rs:99-319, 486-516), native host code (csrc/tz_host_learn.cpp) ----------
  * The two target buffers with forced-use counts (SELFPLAY / REANALYZE_TARGET_FORCED_USES, :59-60) fed by tailing the
  * target files, create_batch (uniform sampling without replacement, a random board symmetry per target, dense
@@ -561,7 +600,8 @@ int tz_learn_run(tz_learn* l, const char* directory, int64_t starting_steps, int
  * `bitvec.bin` beside the model.  0 = no such save point. */
 int tz_learn_set_save_points(tz_learn* l, int steps_per_save, int steps_per_checkpoint, tz_net* hash_net);
 /* RND training inside the loop (learn/src/main.rs:404-405, 415-416): train_rnd != 0 enables it on the loop's trainer
- * (tz_trainer_rnd_enable; 0 disables it), so every step of tz_learn_step / tz_learn_run trains the predictor.  early / late (copied;
+ * (tz_trainer_rnd_enable, or tz_trainer_rnd4_enable / _calibrate when the trainer is TZ_ARCH_NET4_RND; 0 disables it), so every step
+ * of tz_learn_step / tz_learn_run trains the predictor.  early / late (copied;
  * may be NULL with a count of 0) are the reference positions of update_rnd: with them, tz_learn_run calibrates with apply = 1
  * immediately before every model file it writes and before every on_step callback that falls on a multiple of calibrate_every
  * (> 0), so that a saved model's min / max belong to its weights.  The commented-out reference calibrates after every step: two

@@ -44,6 +44,7 @@ SYMBOLS = [
     "tz_search_simulate_batch", "tz_search_principal_variation", "tz_search_batch_profile",
     "tz_search_set_selection", "tz_search_get_selection",
     "tz_trainer_rnd_enable", "tz_trainer_rnd_last", "tz_trainer_rnd_activation", "tz_trainer_rnd_calibrate", "tz_learn_set_rnd",
+    "tz_trainer_rnd4_enable", "tz_trainer_rnd4_last", "tz_trainer_rnd4_activation", "tz_trainer_rnd4_calibrate",
     "tz_learn_rnd_reference",
 ]
 
@@ -199,6 +200,10 @@ def load():
     lib.tz_trainer_rnd_last.argtypes = [vp, C.POINTER(cf), vp]
     lib.tz_trainer_rnd_activation.argtypes = [vp, ci, ci, vp, C.c_uint64]
     lib.tz_trainer_rnd_calibrate.argtypes = [vp, vp, ci, vp, ci, ci, C.POINTER(cf), C.POINTER(cf)]
+    lib.tz_trainer_rnd4_enable.argtypes = [vp, ci]
+    lib.tz_trainer_rnd4_last.argtypes = [vp, C.POINTER(cf), vp]
+    lib.tz_trainer_rnd4_activation.argtypes = [vp, ci, ci, vp, C.c_uint64]
+    lib.tz_trainer_rnd4_calibrate.argtypes = [vp, vp, ci, vp, ci, ci, C.POINTER(cf), C.POINTER(cf)]
     lib.tz_learn_set_rnd.argtypes = [vp, ci, vp, ci, vp, ci, ci]
     lib.tz_learn_rnd_reference.argtypes = [vp, C.c_uint64, ci, ci, ci, ci, vp, vp]
     _lib = lib

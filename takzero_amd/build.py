@@ -25,6 +25,7 @@ UNITS = [
     # net4_rnd's towers on tz_nn.hip's device encoder; its variance is restated by callers: no contraction, rounded division
     ("tz_nn_rnd4.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
     ("tz_learn.hip", ["-ffp-contract=off"]),
+    ("tz_learn_rnd4.hip", ["-ffp-contract=off"]),   # net4_rnd's predictor training beside the trunk's step
 ]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-fno-fast-math", "-Wall", "-Wno-unused-function",
           "-Wno-unused-result"]

@@ -202,9 +202,18 @@ int make_batch(tz_learn* l, bool using_reanalyze, bool augment, int slot) {
     return TZ_OK;
 }
 
+// net4_rnd's predictor is a conv tower with calls of its own (tz_trainer_rnd4_*); net5's MLP keeps tz_trainer_rnd_*
+bool rnd_is_tower(tz_learn* l) {
+    int arch = 0;
+    return tz_trainer_shape(l->trainer, nullptr, nullptr, &arch) == TZ_OK && arch == TZ_ARCH_NET4_RND;
+}
+
 // update_rnd with apply (learn/src/main.rs:415-416), when RND training is on and the loop holds reference positions
 int rnd_calibrate(tz_learn* l) {
     if (!l->train_rnd || l->rnd_early.empty() || l->rnd_late.empty()) return TZ_OK;
+    if (rnd_is_tower(l))
+        return tz_trainer_rnd4_calibrate(l->trainer, l->rnd_early.data(), (int)l->rnd_early.size(), l->rnd_late.data(), (int)l->rnd_late.size(),
+                                         1, nullptr, nullptr);
     return tz_trainer_rnd_calibrate(l->trainer, l->rnd_early.data(), (int)l->rnd_early.size(), l->rnd_late.data(), (int)l->rnd_late.size(), 1,
                                     nullptr, nullptr);
 }
@@ -427,7 +436,7 @@ int tz_learn_set_rnd(tz_learn* l, int train_rnd, const tz_state* early, int n_ea
     if (!l || n_early < 0 || n_late < 0 || (n_early > 0 && !early) || (n_late > 0 && !late) || calibrate_every < 0)
         return tz_fail(TZ_EINVAL, "tz_learn_set_rnd: bad argument");
     if (l->writer.joinable()) l->writer.join();
-    int rc = tz_trainer_rnd_enable(l->trainer, train_rnd ? 1 : 0);
+    int rc = rnd_is_tower(l) ? tz_trainer_rnd4_enable(l->trainer, train_rnd ? 1 : 0) : tz_trainer_rnd_enable(l->trainer, train_rnd ? 1 : 0);
     if (rc) return rc;
     l->train_rnd = train_rnd != 0;
     l->rnd_early.assign(early, early + n_early);

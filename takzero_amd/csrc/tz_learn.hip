@@ -12,7 +12,8 @@
 //   parameters, gradients and the two Adam moments live in four parallel arenas; one Adam launch per step.
 //
 // Optional (tz_trainer_rnd_enable, off by default): net5's RND predictor is trained in the same step (net5.rs:193-218;
-// learn/src/main.rs:404-405) by a chain of small launches on a stream of its own, see "RND distillation" below.
+// learn/src/main.rs:404-405) by a chain of small launches on a stream of its own, see "RND distillation" below.  net4_rnd's predictor
+// tower has the same switch (tz_trainer_rnd4_enable); its kernels are a unit of their own, tz_learn_rnd4.hip.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -23,6 +24,7 @@
 #include <string>
 #include <vector>
 
+#include "tz_learn_rnd4.h"
 #include "tz_nn.h"
 
 namespace {
@@ -1026,6 +1028,7 @@ struct tz_trainer {
     TensorStore extra;
     Rnd rnd;
     Ens ens;
+    Rnd4Learn* rnd4 = nullptr;   // net4_rnd's predictor tower (tz_learn_rnd4.h), created when tz_trainer_rnd4_enable first switches it on
 };
 
 namespace {
@@ -1130,6 +1133,7 @@ int forward(tz_trainer* t) {
     const size_t act = (size_t)M * FILTERS;
     if ((rc = tz_nn_encode_planes(t->n, t->cin, t->states, t->batch, t->x0, t->stream))) return rc;
     if (t->rnd.on) TZ_HIP(hipEventRecord(t->rnd.ev_x0, t->stream));   // the RND chain starts from the planes, beside the trunk
+    if (t->rnd4 && t->rnd4->on) TZ_HIP(hipEventRecord(t->rnd4->ev_x0, t->stream));
     for (int l = 0; l < t->layers; l++) {
         const float* in = l == 0 ? t->x0 : t->a[l - 1];
         const int C = l == 0 ? t->cin : FILTERS, Kp = l == 0 ? t->kp_in : 9 * FILTERS;
@@ -1534,6 +1538,22 @@ int ens_chain(tz_trainer* t, int apply_step) {
     return TZ_OK;
 }
 
+// net4_rnd's distillation step on the tower's own stream (tz_learn_rnd4.hip): it waits for the planes only, and nothing of the trunk's
+// step reads what it writes; the main stream joins before its own Adam launch.  The predictor's group counts its own Adam steps.
+int rnd4_chain(tz_trainer* t, int apply_step) {
+    Rnd4Learn* r = t->rnd4;
+    int rc;
+    if ((rc = tz_rnd4l_chain(r, t->x0, apply_step))) return rc;
+    if (apply_step) {
+        r->t_step++;
+        adam_kernel<<<R4L_TOTAL / 1024, 256, 0, r->stream>>>(r->P, r->G, r->M1, r->M2, r->group, t->lr, 0, 0, r->t_step);
+        if ((rc = launch_check("rnd4 adam"))) return rc;
+    }
+    TZ_HIP(hipEventRecord(r->ev_done, r->stream));
+    return TZ_OK;
+}
+bool rnd4_on(const tz_trainer* t) { return t->rnd4 && t->rnd4->on; }
+
 }  // namespace
 // ------------------------------------------------------------------------------------------------
 // C ABI (include/takzero_hip.h, "Trainer")
@@ -1682,6 +1702,7 @@ int tz_trainer_destroy(tz_trainer* t) {
     }
     if (t->rnd.ev_x0) (void)hipEventDestroy(t->rnd.ev_x0);
     if (t->rnd.ev_done) (void)hipEventDestroy(t->rnd.ev_done);
+    tz_rnd4l_destroy(t->rnd4);
     for (void* q : t->allocs) (void)hipFree(q);
     (void)hipStreamDestroy(t->stream);
     (void)hipStreamDestroy(t->stream2);
@@ -1736,6 +1757,15 @@ int tz_trainer_set_tensor(tz_trainer* t, const char* name, int what, const float
         TZ_HIP(hipMemcpy(ra + r.off[i], host.data(), r.slots[i] * sizeof(float), hipMemcpyHostToDevice));
         return TZ_OK;
     }
+    {
+        size_t off, n;
+        int kind, ci;
+        if (rnd4_on(t) && tz_rnd4l_find(name, off, n, kind, ci)) {   // net4_rnd's predictor tower, while its training is enabled
+            TZ_HIP(hipSetDevice(t->device));
+            TZ_HIP(hipStreamSynchronize(t->stream));
+            return tz_rnd4l_set(t->rnd4, name, what, data, count);
+        }
+    }
     size_t eoff = 0, ecount = 0;
     if (t->ens.armed && ens_find(name, eoff, ecount)) {   // the heads' variables answer while the trainer is armed
         Ens& e = t->ens;
@@ -1782,6 +1812,15 @@ int tz_trainer_get_tensor(tz_trainer* t, const char* name, int what, float* out,
         TZ_HIP(hipMemcpy(host.data(), ra + r.off[i], r.slots[i] * sizeof(float), hipMemcpyDeviceToHost));
         rnd_unpack(i, host, out);
         return TZ_OK;
+    }
+    {
+        size_t off, n;
+        int kind, ci;
+        if (rnd4_on(t) && tz_rnd4l_find(name, off, n, kind, ci)) {
+            TZ_HIP(hipSetDevice(t->device));
+            TZ_HIP(hipStreamSynchronize(t->stream));
+            return tz_rnd4l_get(t->rnd4, name, what, out, count);
+        }
     }
     size_t eoff = 0, ecount = 0;
     if (t->ens.armed && ens_find(name, eoff, ecount)) {
@@ -1833,6 +1872,12 @@ int tz_trainer_snapshot(tz_trainer* t, TensorStore& out) {
         int rc = ens_download(t);
         if (rc) return rc;
     }
+    if (rnd4_on(t)) {
+        TZ_HIP(hipSetDevice(t->device));
+        TZ_HIP(hipStreamSynchronize(t->stream));
+        int rc = tz_rnd4l_download(t->rnd4, t->extra);
+        if (rc) return rc;
+    }
     out = t->extra;
     for (const Param& p : t->params) {
         HostTensor h;
@@ -1864,6 +1909,15 @@ static int trainer_apply_store(tz_trainer* t, const TensorStore& st) {
             return tz_fail(TZ_ESTATE, "trainer: the loaded model holds no ensemble heads; the trainer is disarmed");
         }
         int rc = ens_upload(t);
+        if (rc) return rc;
+    }
+    if (rnd4_on(t)) {   // the loaded model's towers replace the device's (moments stay, as for the other parameters)
+        if (!tz_rnd4l_present(t->extra)) {
+            t->rnd4->on = false;
+            return tz_fail(TZ_ESTATE, "trainer: the loaded model holds no RND towers; their training is switched off");
+        }
+        TZ_HIP(hipStreamSynchronize(t->stream));
+        int rc = tz_rnd4l_upload(t->rnd4, t->extra);
         if (rc) return rc;
     }
     if (t->rnd.on) {   // the loaded model's RND nets replace the device's (moments stay, as for the other parameters)
@@ -1903,6 +1957,12 @@ int tz_trainer_get_extras(tz_trainer* t, void* out, uint64_t cap, uint64_t* byte
     }
     if (t->ens.armed) {
         int rc = ens_download(t);
+        if (rc) return rc;
+    }
+    if (rnd4_on(t)) {
+        TZ_HIP(hipSetDevice(t->device));
+        TZ_HIP(hipStreamSynchronize(t->stream));
+        int rc = tz_rnd4l_download(t->rnd4, t->extra);
         if (rc) return rc;
     }
     std::vector<unsigned char> blob;
@@ -1958,8 +2018,10 @@ int tz_trainer_step(tz_trainer* t, const tz_state* states, const float* target_p
     if ((rc = mirror_all(t))) return rc;
     if ((rc = forward(t))) return rc;
     if (t->rnd.on && (rc = rnd_chain(t, apply_step))) return rc;
+    if (rnd4_on(t) && (rc = rnd4_chain(t, apply_step))) return rc;
     if ((rc = backward(t, train_ube))) return rc;
     if (t->rnd.on) TZ_HIP(hipStreamWaitEvent(t->stream, t->rnd.ev_done, 0));
+    if (rnd4_on(t)) TZ_HIP(hipStreamWaitEvent(t->stream, t->rnd4->ev_done, 0));
     if (t->ens.armed && (rc = ens_chain(t, apply_step))) return rc;
     if (apply_step) {
         t->t_main++;
@@ -1972,6 +2034,7 @@ int tz_trainer_step(tz_trainer* t, const tz_state* states, const float* target_p
     TZ_HIP(hipMemcpyAsync(losses, t->losses, sizeof(float) * 3, hipMemcpyDeviceToHost, t->stream));
     if (t->ens.armed) TZ_HIP(hipMemcpyAsync(&loss_ens, t->ens.loss, sizeof(float), hipMemcpyDeviceToHost, t->stream));
     if (t->rnd.on) TZ_HIP(hipMemcpyAsync(&losses[3], t->rnd.loss, sizeof(float), hipMemcpyDeviceToHost, t->stream));
+    if (rnd4_on(t)) TZ_HIP(hipMemcpyAsync(&losses[3], t->rnd4->loss, sizeof(float), hipMemcpyDeviceToHost, t->stream));
     TZ_HIP(hipStreamSynchronize(t->stream));
     if (t->rnd.on) {
         t->rnd.last_loss = losses[3];
@@ -1981,10 +2044,14 @@ int tz_trainer_step(tz_trainer* t, const tz_state* states, const float* target_p
         t->ens.last_loss = loss_ens;
         t->ens.have_last = true;
     }
+    if (rnd4_on(t)) {
+        t->rnd4->last_loss = losses[3];
+        t->rnd4->have_last = true;
+    }
     if (losses_out) memcpy(losses_out, losses, sizeof(float) * 3);
     if (!(losses[0] == losses[0]) || !(losses[1] == losses[1]) || !(losses[2] == losses[2]))
         return tz_fail(TZ_ENUMERIC, "tz_trainer_step: a loss is NaN");
-    if (t->rnd.on && !(losses[3] == losses[3])) return tz_fail(TZ_ENUMERIC, "tz_trainer_step: loss_rnd is NaN");
+    if ((t->rnd.on || rnd4_on(t)) && !(losses[3] == losses[3])) return tz_fail(TZ_ENUMERIC, "tz_trainer_step: loss_rnd is NaN");
     if (t->ens.armed && !(loss_ens == loss_ens)) return tz_fail(TZ_ENUMERIC, "tz_trainer_step: loss_ensemble is NaN");
     return TZ_OK;
 }
@@ -2127,6 +2194,65 @@ int tz_trainer_rnd_calibrate(tz_trainer* t, const tz_state* early, int n_early, 
     if (min_out) *min_out = found[0];
     if (max_out) *max_out = found[1];
     if (!(found[1] > found[0])) return tz_fail(TZ_ESTATE, "tz_trainer_rnd_calibrate: max is not above min; the variables are left alone");
+    if (apply) {
+        t->extra["min"].data[0] = found[0];
+        t->extra["max"].data[0] = found[1];
+    }
+    return TZ_OK;
+}
+
+// ---- training net4_rnd's predictor tower (net4_rnd.rs:126-166, 210-223; learn/src/main.rs:404-405; learn/src/rnd_normalization.rs:74-78) ----
+int tz_trainer_rnd4_enable(tz_trainer* t, int on) {
+    if (!t) return tz_fail(TZ_EINVAL, "tz_trainer_rnd4_enable: null handle");
+    if (t->arch != TZ_ARCH_NET4_RND) return tz_fail(TZ_EINVAL, "tz_trainer_rnd4_enable: only net4_rnd has RND towers");
+    TZ_HIP(hipSetDevice(t->device));
+    TZ_HIP(hipStreamSynchronize(t->stream));
+    int rc;
+    if (!on) {
+        if (rnd4_on(t) && (rc = tz_rnd4l_download(t->rnd4, t->extra))) return rc;   // the trained predictor stays with the carried variables
+        if (t->rnd4) t->rnd4->on = false;
+        return TZ_OK;
+    }
+    if (rnd4_on(t)) return TZ_OK;
+    if (!tz_rnd4l_present(t->extra))
+        return tz_fail(TZ_ESTATE, "tz_trainer_rnd4_enable: the loaded variables hold no rnd_predictor.* / rnd_target.* / min / max");
+    if (!t->rnd4 && (rc = tz_rnd4l_create(t->batch, t->device, &t->rnd4))) return rc;
+    if ((rc = tz_rnd4l_upload(t->rnd4, t->extra))) return rc;
+    t->rnd4->on = true;
+    return TZ_OK;
+}
+
+int tz_trainer_rnd4_last(tz_trainer* t, float* loss_out, float* raw_out) {
+    if (!t) return tz_fail(TZ_EINVAL, "tz_trainer_rnd4_last: null handle");
+    if (!t->rnd4 || !t->rnd4->have_last) return tz_fail(TZ_ESTATE, "tz_trainer_rnd4_last: no step with the predictor's training yet");
+    TZ_HIP(hipSetDevice(t->device));
+    TZ_HIP(hipStreamSynchronize(t->stream));
+    TZ_HIP(hipStreamSynchronize(t->rnd4->stream));
+    if (loss_out) *loss_out = t->rnd4->last_loss;
+    if (raw_out) TZ_HIP(hipMemcpy(raw_out, t->rnd4->raw, sizeof(float) * t->batch, hipMemcpyDeviceToHost));
+    return TZ_OK;
+}
+
+int tz_trainer_rnd4_activation(tz_trainer* t, int which, int layer, float* out, uint64_t out_cap) {
+    if (!t || !out) return tz_fail(TZ_EINVAL, "tz_trainer_rnd4_activation: null argument");
+    if (!t->rnd4) return tz_fail(TZ_ESTATE, "tz_trainer_rnd4_activation: the predictor's training was never enabled");
+    TZ_HIP(hipSetDevice(t->device));
+    TZ_HIP(hipStreamSynchronize(t->stream));
+    return tz_rnd4l_activation(t->rnd4, which, layer, out, out_cap);
+}
+
+int tz_trainer_rnd4_calibrate(tz_trainer* t, const tz_state* early, int n_early, const tz_state* late, int n_late, int apply,
+                              float* min_out, float* max_out) {
+    if (!t || !early || !late || n_early < 1 || n_late < 1) return tz_fail(TZ_EINVAL, "tz_trainer_rnd4_calibrate: bad argument");
+    if (!rnd4_on(t)) return tz_fail(TZ_ESTATE, "tz_trainer_rnd4_calibrate: the predictor's training is not enabled");
+    TZ_HIP(hipSetDevice(t->device));
+    TZ_HIP(hipStreamSynchronize(t->stream));
+    float found[2];
+    int rc;
+    if ((rc = tz_rnd4l_calibrate(t->rnd4, early, n_early, late, n_late, found))) return rc;
+    if (min_out) *min_out = found[0];
+    if (max_out) *max_out = found[1];
+    if (!(found[1] > found[0])) return tz_fail(TZ_ESTATE, "tz_trainer_rnd4_calibrate: max is not above min; the variables are left alone");
     if (apply) {
         t->extra["min"].data[0] = found[0];
         t->extra["max"].data[0] = found[1];

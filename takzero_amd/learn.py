@@ -51,6 +51,17 @@ class Trainer:
     ENSEMBLE_NAMES = tuple("ensemble head %d.%s" % (i, part) for i in range(api.ENSEMBLE_SIZE)
                            for part in ("conv2d.weight", "conv2d.bias", "linear.weight", "linear.bias"))
 
+    # the variables of net4_rnd's predictor tower (net4_rnd.rs:126-166): LayerNorm weight and bias, then ten times conv weight,
+    # BatchNorm weight and bias (the 32 trained ones), then the 20 running statistics; trained / tracked by the step while
+    # rnd4_enable() is on, and then readable / writable through tensor() (the running statistics with what = PARAM only)
+    RND4_LAYERS = ("input_conv2d|batch_norm",) + tuple("res_block_%d.%s.conv2d|res_block_%d.%s.batch_norm" % (b, h, b, h)
+                                                        for b in range(4) for h in "ab") + ("last_small_block.conv2d|last_small_block.batch_norm",)
+    RND4_TRAINED = ("rnd_predictor.layer_norm.weight", "rnd_predictor.layer_norm.bias") + tuple(
+        "rnd_predictor." + name for layer in RND4_LAYERS for name in
+        (layer.split("|")[0] + ".weight", layer.split("|")[1] + ".weight", layer.split("|")[1] + ".bias"))
+    RND4_STATS = tuple("rnd_predictor.%s.%s" % (layer.split("|")[1], part) for layer in RND4_LAYERS for part in ("running_mean", "running_var"))
+    RND4_NAMES = RND4_TRAINED + RND4_STATS
+
     def __init__(self, arch=api.ARCH_NET5, n=0, blocks=0, batch=BATCH_SIZE, lr=LEARNING_RATE, device=0):
         from . import weights as W
 
@@ -126,6 +137,10 @@ class Trainer:
             out = np.zeros(shape, np.float32)
             check(self.lib.tz_trainer_get_tensor(self.h, name.encode(), what, out.ctypes.data, out.size))
             return out
+        if name in self.RND4_NAMES:
+            out = np.zeros(self._rnd4_shape(name), np.float32)
+            check(self.lib.tz_trainer_get_tensor(self.h, name.encode(), what, out.ctypes.data, out.size))
+            return out
         if name in self.ENSEMBLE_NAMES:
             shape = {"conv2d.weight": (1, 256, 1, 1), "conv2d.bias": (1,), "linear.weight": (1, self.n * self.n),
                      "linear.bias": (1,)}[name.split(".", 1)[1]]
@@ -144,6 +159,50 @@ class Trainer:
         out, inp = {"input_linear": (W.RND_HIDDEN, cin), "hidden_linear": (W.RND_HIDDEN, W.RND_HIDDEN),
                     "final_linear": (W.RND_OUT, W.RND_HIDDEN)}[layer]
         return (out, inp) if part == "weight" else (out,)
+
+    @staticmethod
+    def _rnd4_shape(name):
+        from . import weights as W
+
+        if ".layer_norm." in name:
+            return (28, 4, 4)
+        if name.endswith("conv2d.weight"):
+            return (W.RND4_FILTERS, 28 if name.endswith(".input_conv2d.weight") else W.RND4_FILTERS, 3, 3)
+        return (W.RND4_FILTERS,)
+
+    def rnd4_enable(self, on=True):
+        """tz_trainer_rnd4_enable: the step also trains net4_rnd's predictor tower (loss_rnd, learn/src/main.rs:404-405)."""
+        check(self.lib.tz_trainer_rnd4_enable(self.h, 1 if on else 0))
+        return self
+
+    def rnd4_last(self):
+        """(loss_rnd, forward_rnd(xs, true) [batch]) of the last enabled step, before that step's update."""
+        loss, raw = C.c_float(), np.zeros(self.batch, np.float32)
+        check(self.lib.tz_trainer_rnd4_last(self.h, C.byref(loss), raw.ctypes.data))
+        return float(loss.value), raw
+
+    def rnd4_activation(self, which, layer):
+        """What the last enabled step left in tower `which` (0 predictor, 1 target): layer 0 the LayerNorm output [batch, 28, 4, 4];
+        1..10 a conv layer's output after BatchNorm, residual and ReLU [batch, 16, 32]; 11..20 (predictor) the conv outputs before
+        BatchNorm [batch, 16, 32]."""
+        out = np.zeros((self.batch, 28, 4, 4) if layer == 0 else (self.batch, 16, 32), np.float32)
+        check(self.lib.tz_trainer_rnd4_activation(self.h, which, layer, out.ctypes.data, out.size))
+        return out
+
+    def rnd4_calibrate(self, early, late, apply=True):
+        """update_rnd (learn/src/rnd_normalization.rs:74-78) for net4_rnd: (min over the early states, max over the late ones) of the
+        f32 inference tower on the current variables; with `apply` they become the variables min / max."""
+        e, l = api._states(early), api._states(late)
+        mn, mx = C.c_float(), C.c_float()
+        check(self.lib.tz_trainer_rnd4_calibrate(self.h, e.ctypes.data, len(e), l.ctypes.data, len(l), 1 if apply else 0,
+                                                 C.byref(mn), C.byref(mx)))
+        return float(mn.value), float(mx.value)
+
+    def _rnd_calls(self):
+        """(enable, calibrate) of the trainer's RND predictor: net4_rnd's tower or net5's MLP."""
+        if self.arch == api.ARCH_NET4_RND:
+            return self.rnd4_enable, self.rnd4_calibrate
+        return self.rnd_enable, self.rnd_calibrate
 
     def set_tensor(self, name, data, what=PARAM):
         """One trained variable (a name of `names`, or of RND_NAMES while RND training is enabled) in the reference's layout."""
@@ -433,7 +492,7 @@ def run_learn(directory, trainer, half_komi=4, steps=None, seed=0, pre_train_mct
               max_wait=None, log=None, train_rnd=False, rnd_reference=None, rnd_calibrate_every=0):
     """learn::main (:99-270).  `trainer` must already hold initial weights (Net::new) unless the directory has a
     model_<steps>.ot to resume from.  Returns the number of training steps the model has seen.
-    train_rnd: the steps of the main loop also train the RND predictor (:404-405); rnd_reference = (early, late) states: update_rnd
+    train_rnd: the steps of the main loop also train the RND predictor (net5's MLP or net4_rnd's tower, :404-405); rnd_reference = (early, late) states: update_rnd
     (:415-416) runs before every model file written from then on and every rnd_calibrate_every steps (0: only before files)."""
     import os
     import time
@@ -446,7 +505,7 @@ def run_learn(directory, trainer, half_komi=4, steps=None, seed=0, pre_train_mct
 
     def calibrate():
         if train_rnd and rnd_reference is not None:
-            trainer.rnd_calibrate(rnd_reference[0], rnd_reference[1], apply=True)
+            trainer._rnd_calls()[1](rnd_reference[0], rnd_reference[1], apply=True)
 
     saver = AsyncAppender()   # model files are written behind the training loop, in order
     resume = model_path_with_most_steps(directory)
@@ -477,7 +536,7 @@ def run_learn(directory, trainer, half_komi=4, steps=None, seed=0, pre_train_mct
             starting_steps += pre_training_steps
             save_model(trainer, os.path.join(directory, "model_%07d.ot" % starting_steps), hash_net)
     if train_rnd:
-        trainer.rnd_enable(True)
+        trainer._rnd_calls()[0](True)
     calibrate()
     save_model(trainer, os.path.join(directory, "model_latest.ot"), hash_net)
     exploitation = TargetBuffer(n, half_komi, SELFPLAY_TARGET_FORCED_USES)
@@ -641,7 +700,7 @@ def run_learn_native(directory, trainer, half_komi=4, steps=None, seed=0, pre_tr
     """learn::main (learn/src/main.rs:99-270) with the buffers, batch construction and loop in native code; this function
     keeps what touches files in the reference's formats through host tools: model discovery / resume and the save
     points (LibTorch archives).
-    train_rnd: the steps of the main loop also train the RND predictor (:404-405); rnd_reference = (early, late) states
+    train_rnd: the steps of the main loop also train the RND predictor (net5's MLP or net4_rnd's tower, :404-405); rnd_reference = (early, late) states
     (rnd_reference() makes them): update_rnd (:415-416) runs before every model file written from then on and every
     rnd_calibrate_every steps (0: only before files)."""
     import os
@@ -684,7 +743,7 @@ def run_learn_native(directory, trainer, half_komi=4, steps=None, seed=0, pre_tr
             loop.set_rnd(True, rnd_reference[0] if have_reference else None, rnd_reference[1] if have_reference else None,
                          rnd_calibrate_every)
         if have_reference:
-            trainer.rnd_calibrate(rnd_reference[0], rnd_reference[1], apply=True)
+            trainer._rnd_calls()[1](rnd_reference[0], rnd_reference[1], apply=True)
         save_model(trainer, os.path.join(directory, "model_latest.ot"), hash_net)
 
         def on_step(step_no, losses, states):
@@ -693,7 +752,7 @@ def run_learn_native(directory, trainer, half_komi=4, steps=None, seed=0, pre_tr
             if log:
                 log("step %d: loss_policy %.5f loss_value %.5f loss_ube %.5f" % ((step_no,) + tuple(losses)))
             if have_reference and (step_no % steps_per_save == 0 or step_no % steps_per_checkpoint == 0):
-                trainer.rnd_calibrate(rnd_reference[0], rnd_reference[1], apply=True)
+                trainer._rnd_calls()[1](rnd_reference[0], rnd_reference[1], apply=True)
             if step_no % steps_per_save == 0:
                 save_model(trainer, os.path.join(directory, "model_latest.ot"), hash_net, saver)
             if step_no % steps_per_checkpoint == 0:
