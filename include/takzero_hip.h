@@ -332,6 +332,16 @@ int tz_search_ube_target(tz_search* s, float beta, float* out /*[batch]*/);
 /* BatchedMCTS::step (batched.rs:131-144): descend (subtree reuse) + env.step; skipped for
  * terminal roots.  actions[batch] are move indices. */
 int tz_search_step(tz_search* s, const uint16_t* actions);
+/* tz_search_step for a tree of an engine's size.  tz_search_step copies a game's kept subtree with one wave, which suits
+ * thousands of small trees; this call takes the games one after another and gives each the whole device: per level of the kept
+ * subtree, a scan of the parents' child counts in blocks of TZ_STEP_WIDE_BLOCK, one wave that scans the block sums
+ * TZ_STEP_WIDE_SUMS at a time, and one thread per child copied; the host reads the level's child count (4 bytes) to size the next
+ * launches.  Everything a caller can observe is what tz_search_step leaves: trees (slot for slot), positions, pool usage,
+ * counters, errors; the handle's captured simulation graphs stay valid.  Scratch of 4 bytes per node slot of one game is
+ * allocated at the first call. */
+#define TZ_STEP_WIDE_BLOCK 128
+#define TZ_STEP_WIDE_SUMS 64
+int tz_search_step_wide(tz_search* s, const uint16_t* actions);
 /* BatchedMCTS::restart_terminal_envs (batched.rs:185-203): finished games get a fresh opening
  * (opening_choice as above) and a fresh tree; terminal_out[g] = TZ_TERMINAL_* of the game
  * that ended, TZ_TERMINAL_NONE otherwise. */
@@ -616,6 +626,103 @@ int tz_learn_set_rnd(tz_learn* l, int train_rnd, const tz_state* early, int n_ea
  * reference keeps the terminal position, which is unpinned too). */
 int tz_learn_rnd_reference(tz_search* search, uint64_t seed, int n_early, int early_ply, int n_late, int late_ply,
                            tz_state* early_out, tz_state* late_out);
+
+/* ---------- tei: the reference's engine binary (tei/src/main.rs, tei/src/protocol.rs), native host code (csrc/tz_tei.cpp) ----------
+ * A UCI-style text engine over ONE tree: the session keeps a game, replays `position` commands with tree reuse
+ * (tz_search_step_wide), and searches with tz_search_simulate_batch(leaves, rounds = 1) at beta 0 until a node count, a move time
+ * or a stop ends it (main.rs:139-297).  examples/tei_cli.cpp is the program around it (handshake, reader thread).
+ *
+ * tz_tei_create: one_tree must have a batch of 1 (else TZ_EINVAL) and a net or dummy agent; leaves is BATCH_SIZE of main.rs:26
+ * (128).  Like the reference (main.rs:141) it runs one simulation on the start position.  The session borrows the handle; destroy
+ * the session first.
+ *
+ * tz_tei_line: one input line after the handshake (isready, teinewgame N, position startpos|tps ... [moves ...], go ..., stop,
+ * quit; tei and setoption get a warning).  The output lines, each ended by '\n', are written to out[cap] with a final NUL;
+ * *size_out = their length (if it exceeds cap - 1, out holds the first cap - 1 bytes).  *quit_out = 1 when the program should end.
+ * `go` returns when the search has ended, with its info line or lines and `bestmove`.  What the reference writes to its log
+ * (stderr) comes out as `info string error: ...` / `info string warning: ...` lines.  An unparsable line is TZ_EPARSE with such a
+ * line; the session is unchanged.
+ *
+ * `position`: when the position equals the last one and the move list starts with the last move list, the tree is kept
+ * (main.rs:174-184): every new move must be among the root's children and is applied with tz_search_step_wide; on a root without
+ * children it goes through tz_search_play_moves, which validates it and resets the tree (Node::descend on a childless node).
+ * Otherwise the tree is reset, the position set and the moves played with tz_search_play_moves.  A move that is not legal stops
+ * the replay with an error line.
+ *
+ * `go`: nodes N, movetime ms, infinite, and wtime / btime / winc / binc taken for the side to move only (:216-236); with both the
+ * mover's time and increment and no movetime, movetime = time / 10 + 3 * inc / 4 (:241-243).  After every round: visits = root
+ * visits - visits at the start; done when visits >= nodes or elapsed >= movetime; an info line when the info interval has passed
+ * (:251-279).  At the end an info line if none was sent, then `bestmove` (tz_search_select_best_actions); the limits are cleared.
+ *
+ * Where the session leaves the reference:
+ *   - nps is 0 when the time is 0 ms (the reference divides by zero);
+ *   - teinewgame also forgets the last position and move list (the reference keeps them, and a new game whose moves extend the
+ *     old list would be replayed from the wrong position); so does a `position` whose replay met an illegal move;
+ *   - `go` on a root without children (a terminal position; an over-wide one is TZ_ECAPACITY from the search call) gives no
+ *     bestmove: an `info string` line and TZ_ESTATE;
+ *   - before every round, if capacity - max_used < leaves * max_actions (tz_search_pool_usage, tz_search_shape; the most one
+ *     round can allocate) the search ends as `stop` would, with `info string node pool full`: the reference's heap has no bound,
+ *     and expansions skipped silently (tz_search_pool_overflows) would make a long think worthless;
+ *   - a `stop` line outside a search prints nothing (the reference prints an info line and a bestmove).
+ *
+ * tz_tei_stop is the only call allowed from a second thread while tz_tei_line runs.  It announces a `stop` or `quit` line that the
+ * caller passes to tz_tei_line in its turn: a search ends after the round in progress while a stop has been announced whose line
+ * has not been passed yet.  (So `go`, `stop`, `go`, `stop` read faster than they are handled end both searches, and a `stop` that
+ * arrives between two searches does not cut the second one short.)
+ *
+ * tz_tei_set_sink: with a sink, the info lines of a search go to sink(user, line) as they arise (line without '\n') instead of
+ * to `out`; a non-zero return ends the search as `stop` would.  tz_tei_set_info_interval: milliseconds between info lines,
+ * default 300 (main.rs:24). */
+typedef struct tz_tei tz_tei;
+int tz_tei_create(tz_search* one_tree, int leaves, tz_tei** out);
+int tz_tei_destroy(tz_tei* t);
+int tz_tei_line(tz_tei* t, const char* line, char* out, uint64_t cap, uint64_t* size_out, int* quit_out);
+int tz_tei_stop(tz_tei* t);
+int tz_tei_set_sink(tz_tei* t, int (*sink)(void*, const char*), void* user);
+int tz_tei_set_info_interval(tz_tei* t, int ms);
+/* Input::from_str (protocol.rs:74-160) for board size n, without a device.  *kind_out = TZ_TEI_*; numbers_out[8]:
+ *   teinewgame: [0] = size;  position: [0] = 0 startpos, 1 tps (tps_out = the three TPS words joined by spaces), moves_out /
+ *   *n_moves_out = the move indices (TZ_EINVAL if more than moves_cap);  setoption: tps_out = "<name> <value>";
+ *   go: [0] = mask of the options given, bit TZ_TEI_GO_*; [1 + TZ_TEI_GO_*] = the option's number (ms, or nodes).
+ * A line that does not parse returns TZ_EPARSE with *kind_out = TZ_TEI_ERROR, numbers_out[0] = TZ_TEI_ERR_* (ParseInputError) and
+ * its text in tz_last_error. */
+#define TZ_TEI_ERROR (-1)
+#define TZ_TEI_TEI 0
+#define TZ_TEI_ISREADY 1
+#define TZ_TEI_SETOPTION 2
+#define TZ_TEI_NEWGAME 3
+#define TZ_TEI_POSITION 4
+#define TZ_TEI_GO 5
+#define TZ_TEI_STOP 6
+#define TZ_TEI_QUIT 7
+#define TZ_TEI_GO_WTIME 0
+#define TZ_TEI_GO_BTIME 1
+#define TZ_TEI_GO_WINC 2
+#define TZ_TEI_GO_BINC 3
+#define TZ_TEI_GO_MOVETIME 4
+#define TZ_TEI_GO_NODES 5
+#define TZ_TEI_GO_INFINITE 6
+#define TZ_TEI_ERR_MISSING_FIRST_WORD 1
+#define TZ_TEI_ERR_MISSING_NAME 2
+#define TZ_TEI_ERR_MISSING_VALUE 3
+#define TZ_TEI_ERR_MISSING_SIZE 4
+#define TZ_TEI_ERR_PARSE_INT 5  /* ParseSize: every number of the protocol (ParseIntError) */
+#define TZ_TEI_ERR_MISSING_POSITION 6
+#define TZ_TEI_ERR_MISSING_TPS 7
+#define TZ_TEI_ERR_PARSE_TPS 8
+#define TZ_TEI_ERR_PARSE_MOVE 9
+#define TZ_TEI_ERR_MISSING_SECONDS 10
+#define TZ_TEI_ERR_MISSING_AMOUNT 11
+#define TZ_TEI_ERR_UNRECOGNIZED 12
+int tz_tei_parse(const char* line, int n, int* kind_out, int64_t* numbers_out, uint16_t* moves_out, int moves_cap, int* n_moves_out,
+                 char* tps_out, int tps_cap);
+/* Output::Info's Display (protocol.rs:240-274): "info time <ms> nodes <n> nps <1000 * n / ms> wdl <w> <d> <l>[ score mate <+-m>]
+ * score cp <c> pv <moves in PTN>": wdl 1000 0 0 / 0 0 1000 / 0 1000 0 for Win / Loss / Draw and 500 + round(v * 500), 0, the rest
+ * for a value v; score mate +-ceil(ply / 2) for a proven win or loss only; cp = round(f32::from(eval) * 100), halves away from
+ * zero, f32::from(Eval) being the value or +-0.997^ply (0 for a draw).  Without a device.  Returns the length written (without the
+ * NUL), TZ_EINVAL if cap is too small. */
+int tz_tei_format_info(int n, uint64_t time_ms, uint64_t nodes, uint8_t eval_tag, uint32_t eval_bits, const uint16_t* pv, int pv_len,
+                       char* out, int cap);
 
 /* Diagnostic: evaluates on the device the f32 primitives the tree kernels must compute exactly as
  * the host does (op 0 exp, 1 ln, 2 sqrt, 3 a/b, 4 0.997^int(a), 5 (a+b)*a). */

@@ -46,9 +46,13 @@ SYMBOLS = [
     "tz_trainer_rnd_enable", "tz_trainer_rnd_last", "tz_trainer_rnd_activation", "tz_trainer_rnd_calibrate", "tz_learn_set_rnd",
     "tz_trainer_rnd4_enable", "tz_trainer_rnd4_last", "tz_trainer_rnd4_activation", "tz_trainer_rnd4_calibrate",
     "tz_learn_rnd_reference",
+    "tz_search_step_wide",
+    "tz_tei_create", "tz_tei_destroy", "tz_tei_line", "tz_tei_stop", "tz_tei_set_sink", "tz_tei_set_info_interval", "tz_tei_parse",
+    "tz_tei_format_info",
 ]
 
 _lib = None
+TEI_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p)  # tz_tei_set_sink's callback
 
 
 class TakzeroError(RuntimeError):
@@ -135,6 +139,7 @@ def load():
     lib.tz_search_improved_policy_each.argtypes = [vp, vp, ci, vp]
     lib.tz_search_ube_target.argtypes = [vp, cf, vp]
     lib.tz_search_step.argtypes = [vp, vp]
+    lib.tz_search_step_wide.argtypes = [vp, vp]
     lib.tz_search_restart_terminal.argtypes = [vp, vp, vp]
     lib.tz_search_gumbel_sh.argtypes = [vp, vp, ci, ci, vp, ci, vp]
     lib.tz_search_counters.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -206,6 +211,14 @@ def load():
     lib.tz_trainer_rnd4_calibrate.argtypes = [vp, vp, ci, vp, ci, ci, C.POINTER(cf), C.POINTER(cf)]
     lib.tz_learn_set_rnd.argtypes = [vp, ci, vp, ci, vp, ci, ci]
     lib.tz_learn_rnd_reference.argtypes = [vp, C.c_uint64, ci, ci, ci, ci, vp, vp]
+    lib.tz_tei_create.argtypes = [vp, ci, C.POINTER(vp)]
+    lib.tz_tei_destroy.argtypes = [vp]
+    lib.tz_tei_line.argtypes = [vp, C.c_char_p, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(ci)]
+    lib.tz_tei_stop.argtypes = [vp]
+    lib.tz_tei_set_sink.argtypes = [vp, TEI_SINK, vp]
+    lib.tz_tei_set_info_interval.argtypes = [vp, ci]
+    lib.tz_tei_parse.argtypes = [C.c_char_p, ci, C.POINTER(ci), vp, vp, ci, C.POINTER(ci), vp, ci]
+    lib.tz_tei_format_info.argtypes = [ci, C.c_uint64, C.c_uint64, C.c_uint8, C.c_uint32, vp, ci, vp, ci]
     _lib = lib
     return lib
 

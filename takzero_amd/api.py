@@ -438,6 +438,13 @@ class BatchedMCTS:
         assert a.shape == (self.batch,)
         check(self.lib.tz_search_step(self.h, a.ctypes.data))
 
+    def step_wide(self, actions):
+        """step() for a tree of an engine's size: the same result, the copy of each kept subtree spread over the device
+        (tz_search_step_wide)."""
+        a = np.ascontiguousarray(actions, dtype=np.uint16)
+        assert a.shape == (self.batch,)
+        check(self.lib.tz_search_step_wide(self.h, a.ctypes.data))
+
     def restart_terminal_envs(self, opening_choice):
         c = np.ascontiguousarray(opening_choice, dtype=np.int32)
         out = np.zeros(self.batch, np.int8)
@@ -479,6 +486,75 @@ class BatchedMCTS:
         cm, cl, tm, st = C.c_double(), C.c_uint64(), C.c_double(), C.c_uint64()
         check(self.lib.tz_search_profile(self.h, reset, C.byref(cm), C.byref(cl), C.byref(tm), C.byref(st)))
         return dict(conv_ms=cm.value, conv_launches=cl.value, tree_ms=tm.value, steps=st.value)
+
+
+class Tei:
+    """The engine session of the reference's tei binary (tei/src/main.rs:139-297) over a one-game BatchedMCTS: line() takes one
+    protocol line (isready, teinewgame N, position ..., go ..., stop, quit) and returns the output lines; `go` returns when the
+    search has ended.  stop() may be called from another thread while line() runs; pass the `stop` line it announces to line()
+    afterwards (tz_tei_stop).  sink(text): receives a search's info lines as they arise, in place of line()'s result; a true
+    return ends the search."""
+
+    def __init__(self, mcts, leaves=128, sink=None):
+        self.lib = _lib.load()
+        self.mcts = mcts  # borrowed by the session
+        h = C.c_void_p()
+        check(self.lib.tz_tei_create(mcts.h, leaves, C.byref(h)))
+        self.h = h
+        self.quit = False
+        self._buf = C.create_string_buffer(1 << 20)
+        self._sink = None
+        if sink is not None:
+            self._sink = _lib.TEI_SINK(lambda user, text: 1 if sink(text.decode()) else 0)
+            check(self.lib.tz_tei_set_sink(self.h, self._sink, None))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.tz_tei_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def line(self, text):
+        size, quit_ = C.c_uint64(0), C.c_int(0)
+        rc = self.lib.tz_tei_line(self.h, text.encode(), self._buf, len(self._buf), C.byref(size), C.byref(quit_))
+        self.quit = self.quit or bool(quit_.value)
+        self.last_lines = self._buf.value.decode().splitlines()
+        check(rc)
+        return self.last_lines
+
+    def stop(self):
+        check(self.lib.tz_tei_stop(self.h))
+
+    def set_info_interval(self, ms):
+        check(self.lib.tz_tei_set_info_interval(self.h, ms))
+
+
+def tei_parse(line, n):
+    """Input::from_str of the tei protocol (tz_tei_parse): (kind, numbers[8], move indices, text)."""
+    lib = _lib.load()
+    kind, n_moves = C.c_int(0), C.c_int(0)
+    numbers = np.zeros(8, np.int64)
+    moves = np.zeros(1024, np.uint16)
+    text = C.create_string_buffer(512)
+    check(lib.tz_tei_parse(line.encode(), n, C.byref(kind), numbers.ctypes.data, moves.ctypes.data, len(moves), C.byref(n_moves),
+                           text, len(text)))
+    return kind.value, numbers, moves[:n_moves.value].copy(), text.value.decode()
+
+
+def tei_format_info(n, time_ms, nodes, eval_tag, eval_bits, pv):
+    """Output::Info's Display of the tei protocol (tz_tei_format_info)."""
+    lib = _lib.load()
+    p = np.ascontiguousarray(pv, dtype=np.uint16)
+    out = C.create_string_buffer(8192)
+    rc = lib.tz_tei_format_info(n, time_ms, nodes, int(eval_tag), int(eval_bits), p.ctypes.data if len(p) else None, len(p), out, len(out))
+    if rc < 0:
+        check(rc)
+    return out.value.decode()
 
 
 def eval_sort_keys(tags, bits):

@@ -15,6 +15,7 @@ UNITS = [
     ("tz_host.cpp", ["-ffp-contract=off"]),
     ("tz_host_learn.cpp", ["-ffp-contract=off"]),
     ("tz_comm.cpp", []),
+    ("tz_tei.cpp", ["-ffp-contract=off"]),   # the engine session: its score arithmetic is restated by callers
     ("tz_tree.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
     ("tz_capi.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
     ("tz_nn.hip", []),

@@ -35,6 +35,8 @@ struct tz_search {
     // tz_search_simulate_batch: leaf slots, allocated at first use and grown on demand
     LeafBatchDev lb = {};
     size_t lb_slots = 0;
+    // tz_search_step_wide: scan scratch, allocated at first use
+    StepWideDev sw = {};
     // with profiling on, HIP events around the three parts of every round: forward (+ compaction), network, backward
     std::vector<std::array<hipEvent_t, 4>> batch_events;
     double batch_ms[3] = {0.0, 0.0, 0.0};
@@ -375,7 +377,8 @@ int tz_search_destroy(tz_search* s) {
                     d.t.action, d.bank, d.alloc, d.env, d.betas, d.traj, d.traj_len, d.start_node, d.leaf_kind,
                     d.leaf_nact, d.leaf_act, d.leaf_env, d.nn_game, d.nn_count, d.bfs_src, d.counters, d.error_flag,
                     d.term_reason, d.term_winner,
-                    s->noise_dev, s->act_dev, s->i32_dev, s->i8_dev, s->info_dev, s->child_dev};
+                    s->noise_dev, s->act_dev, s->i32_dev, s->i8_dev, s->info_dev, s->child_dev,
+                    s->sw.off, s->sw.sums, s->sw.total, s->sw.status};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     free_leaf_batch(s);
@@ -755,6 +758,50 @@ int tz_search_step(tz_search* s, const uint16_t* actions) {
     TZ_HIP(hipMemcpyAsync(s->act_dev, actions, s->d.batch * sizeof(uint16_t), hipMemcpyHostToDevice, s->stream));
     int rc = tz_tree_step(s->d, s->act_dev, s->stream);
     if (rc) return rc;
+    return check_error_flag(s);
+}
+
+// tz_search_step with the copy of each kept subtree spread over the device: games one after another, one level per round of
+// launches, the level's child count read back to size the next (tz_tree.hip, step_wide_*_kernel)
+int tz_search_step_wide(tz_search* s, const uint16_t* actions) {
+    if (!s || !actions) return tz_fail(TZ_EINVAL, "tz_search_step_wide: null argument");
+    TZ_HIP(hipSetDevice(s->device));
+    const int B = s->d.batch;
+    if (!s->sw.off) {
+        StepWideDev w = {};
+        int rc = 0;
+        rc |= dev_alloc(&w.off, (size_t)s->d.cap);
+        rc |= dev_alloc(&w.sums, (size_t)s->d.cap / TZ_STEP_WIDE_BLOCK + 1);
+        rc |= dev_alloc(&w.total, 1);
+        rc |= dev_alloc(&w.status, (size_t)B);
+        if (rc) {
+            void* ptrs[] = {w.off, w.sums, w.total, w.status};
+            for (void* p : ptrs)
+                if (p) (void)hipFree(p);
+            return tz_fail(TZ_ENOMEM, "tz_search_step_wide: device allocation failed");
+        }
+        s->sw = w;
+    }
+    TZ_HIP(hipMemcpyAsync(s->act_dev, actions, B * sizeof(uint16_t), hipMemcpyHostToDevice, s->stream));
+    int rc = tz_tree_step_wide_roots(s->d, s->act_dev, s->sw.status, s->stream);
+    if (rc) return rc;
+    std::vector<uint32_t> status(B);
+    TZ_HIP(hipMemcpyAsync(status.data(), s->sw.status, B * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    TZ_HIP(hipStreamSynchronize(s->stream));
+    for (int g = 0; g < B; g++) {
+        if (!status[g]) continue;
+        uint32_t lo = 0, n = 1;  // the level [lo, lo + n) of the destination whose children are copied next
+        while (n) {
+            if ((rc = tz_tree_step_wide_scan(s->d, s->sw, g, lo, n, s->stream))) return rc;
+            uint32_t total = 0;
+            TZ_HIP(hipMemcpyAsync(&total, s->sw.total, 4, hipMemcpyDeviceToHost, s->stream));
+            TZ_HIP(hipStreamSynchronize(s->stream));
+            if (total > (uint32_t)s->d.cap - (lo + n)) return tz_fail(TZ_EDEVICE, "tz_search_step_wide: level total out of range");
+            if (total && (rc = tz_tree_step_wide_copy(s->d, s->sw, g, lo, n, total, s->stream))) return rc;
+            lo += n;
+            n = total;
+        }
+    }
     return check_error_flag(s);
 }
 

@@ -83,6 +83,14 @@ struct LeafBatchDev {
     int32_t* index;      // [batch * leaves] net slot -> leaf slot
 };
 
+// Scratch of tz_search_step_wide, allocated at its first call: one level of one game at a time
+struct StepWideDev {
+    uint32_t* off;     // [cap] a parent's child offset within its block of TZ_STEP_WIDE_BLOCK parents
+    uint32_t* sums;    // [cap / TZ_STEP_WIDE_BLOCK + 1] block totals, then their exclusive sums
+    uint32_t* total;   // [1] children of the level
+    uint32_t* status;  // [batch] 1: the game keeps a subtree that has to be copied
+};
+
 // network outputs consumed by the expand kernel (device pointers, indexed by nn slot)
 struct NetOut {
     const float* policy;  // [slots][NN][policy_stride]  (NHWC: pixel-major, channel contiguous)
@@ -104,6 +112,9 @@ int tz_tree_node(const SearchDev& s, int game, const uint16_t* path_dev, int len
                  hipStream_t st);
 int tz_tree_select_best(const SearchDev& s, uint16_t* out_dev, hipStream_t st);
 int tz_tree_step(const SearchDev& s, const uint16_t* actions_dev, hipStream_t st);
+int tz_tree_step_wide_roots(const SearchDev& s, const uint16_t* actions_dev, uint32_t* status_dev, hipStream_t st);
+int tz_tree_step_wide_scan(const SearchDev& s, const StepWideDev& w, int game, uint32_t lo, uint32_t n, hipStream_t st);
+int tz_tree_step_wide_copy(const SearchDev& s, const StepWideDev& w, int game, uint32_t lo, uint32_t n, uint32_t total, hipStream_t st);
 int tz_tree_restart(const SearchDev& s, const int32_t* choice_dev, int8_t* terminal_dev, bool force_all,
                     bool with_opening_moves, hipStream_t st);
 int tz_tree_reset_games(const SearchDev& s, const int32_t* idx_dev, int count, hipStream_t st);

@@ -1133,6 +1133,134 @@ __global__ __launch_bounds__(64) void step_kernel(SearchDev s, const uint16_t* a
     }
 }
 
+// ---- tz_search_step_wide: step_kernel's copy, one level of the kept subtree per launch, over the whole device --------------
+// step_kernel lays the kept subtree out in plain breadth-first order: level L is a contiguous range [lo, hi) of the destination and
+// level L + 1 is the children of level L in parent order, starting at hi.  So a level is an exclusive scan of the parents' nchild
+// (block scan, scan of the block sums, offsets applied by the readers) and one thread per child; the level boundary is the
+// kernel boundary and the host reads the level's total to size the next launches.  Every byte written is what step_kernel writes.
+
+// Everything of step_kernel but the copy below the new root, for every game: status[g] = 1 iff a subtree is left to copy.
+template <int N>
+__global__ __launch_bounds__(64) void step_wide_root_kernel(SearchDev s, const uint16_t* actions, uint32_t* status) {
+    const int g = blockIdx.x, l = lane_id();
+    __shared__ tz_state env;
+    const int sbank = s.bank[g], dbank = 1 - sbank;
+    const size_t sb = slab_base(s, sbank, g), db = slab_base(s, dbank, g);
+    if (s.t.eval_tag[sb] != TZ_EVAL_VALUE && s.t.eval_bits[sb] == 0) {  // root.is_terminal()
+        if (l == 0) status[g] = 0;
+        return;
+    }
+    const int action = actions[g];
+    const int nc = s.t.nchild[sb];
+    const uint32_t c0 = s.t.child0[sb];
+    int found = -1;
+    for (int i = l; i < nc; i += 64)
+        if (s.t.action[sb + c0 + i] == action) found = i;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const int o = __shfl_xor(found, d);
+        found = o > found ? o : found;
+    }
+    if (l == 0) {
+        if (found < 0) {
+            write_default_node(s, db);
+        } else {
+            copy_node(s, db, sb + c0 + found);
+            s.bfs_src[(size_t)g * s.cap] = c0 + (uint32_t)found;
+        }
+        status[g] = found < 0 ? 0 : 1;
+    }
+    load_state(&env, &s.env[g]);
+    __syncthreads();
+    apply_move<N>(&env, action);
+    __syncthreads();
+    {
+        const uint32_t* a = reinterpret_cast<const uint32_t*>(&env);
+        uint32_t* b = reinterpret_cast<uint32_t*>(&s.env[g]);
+        for (int i = l; i < (int)(sizeof(tz_state) / 4); i += 64) b[i] = a[i];
+    }
+    if (l == 0) {
+        s.bank[g] = (uint8_t)dbank;  // the level kernels below find the source in the other bank
+        s.alloc[g] = 1;
+    }
+}
+
+// Level [lo, lo + n) of game g's destination: off[i] = exclusive sum of nchild of the parents before parent i within its block of
+// TZ_STEP_WIDE_BLOCK, sums[b] = block b's total.
+__global__ __launch_bounds__(TZ_STEP_WIDE_BLOCK) void step_wide_scan_kernel(SearchDev s, StepWideDev w, int g, uint32_t lo, uint32_t n) {
+    __shared__ int wave_total[TZ_STEP_WIDE_BLOCK / 64];
+    const int t = threadIdx.x, l = lane_id(), wv = t >> 6;
+    const uint32_t i = blockIdx.x * (uint32_t)TZ_STEP_WIDE_BLOCK + t;
+    const size_t sb = slab_base(s, 1 - s.bank[g], g);
+    const uint32_t* bsrc = s.bfs_src + (size_t)g * s.cap;
+    const int cn = i < n ? (int)s.t.nchild[sb + bsrc[lo + i]] : 0;
+    const int incl = wave_incl_scan(cn);
+    if (l == 63) wave_total[wv] = incl;
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int k = 0; k < TZ_STEP_WIDE_BLOCK / 64; k++) {
+        before += k < wv ? wave_total[k] : 0;
+        total += wave_total[k];
+    }
+    if (i < n) w.off[i] = (uint32_t)(before + incl - cn);
+    if (t == 0) w.sums[blockIdx.x] = (uint32_t)total;
+}
+
+// One wave turns the nb block sums into exclusive sums, TZ_STEP_WIDE_SUMS at a time with a carry, and leaves the level's total
+// in *w.total (0 and the overflow flag when it would not fit; the destination has the source's capacity, so it fits).
+__global__ __launch_bounds__(TZ_STEP_WIDE_SUMS) void step_wide_sums_kernel(SearchDev s, StepWideDev w, int g, uint32_t hi, uint32_t nb) {
+    const int l = lane_id();
+    uint32_t carry = 0;
+    for (uint32_t b0 = 0; b0 < nb; b0 += TZ_STEP_WIDE_SUMS) {
+        const uint32_t b = b0 + l;
+        const int v = b < nb ? (int)w.sums[b] : 0;
+        const int incl = wave_incl_scan(v);
+        if (b < nb) w.sums[b] = carry + (uint32_t)(incl - v);
+        carry += (uint32_t)__shfl(incl, 63);
+    }
+    if (l == 0) {
+        if (hi + carry > (uint32_t)s.cap) {
+            atomicMax(s.error_flag, 1);
+            carry = 0;
+        }
+        *w.total = carry;
+        s.alloc[g] = hi + carry;
+    }
+}
+
+// One thread per child c of the level's `total`: its parent is the last i with offset(i) <= c, found in the block sums and then
+// in the block's offsets; thread i < n also writes child0 of parent i.
+__global__ __launch_bounds__(256) void step_wide_copy_kernel(SearchDev s, StepWideDev w, int g, uint32_t lo, uint32_t n, uint32_t total) {
+    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
+    const int dbank = s.bank[g];
+    const size_t sb = slab_base(s, 1 - dbank, g), db = slab_base(s, dbank, g);
+    uint32_t* bsrc = s.bfs_src + (size_t)g * s.cap;
+    const uint32_t hi = lo + n;
+    if (c < n) {
+        const uint32_t src = bsrc[lo + c];
+        if (s.t.nchild[sb + src]) s.t.child0[db + lo + c] = hi + w.sums[c / TZ_STEP_WIDE_BLOCK] + w.off[c];
+    }
+    if (c >= total) return;
+    const uint32_t nb = (n + TZ_STEP_WIDE_BLOCK - 1) / TZ_STEP_WIDE_BLOCK;
+    uint32_t a = 0, z = nb;  // sums[a] <= c < sums[z] (sums[nb] = total)
+    while (z - a > 1) {
+        const uint32_t m = (a + z) >> 1;
+        if (w.sums[m] <= c) a = m; else z = m;
+    }
+    const uint32_t r = c - w.sums[a];
+    const uint32_t first = a * TZ_STEP_WIDE_BLOCK;
+    uint32_t p = first, q = first + TZ_STEP_WIDE_BLOCK < n ? first + TZ_STEP_WIDE_BLOCK : n;  // off[p] <= r < off[q]
+    while (q - p > 1) {
+        const uint32_t m = (p + q) >> 1;
+        if (w.off[m] <= r) p = m; else q = m;
+    }
+    const uint32_t k = r - w.off[p];
+    const uint32_t from = s.t.child0[sb + bsrc[lo + p]] + k;
+    copy_node(s, db + hi + c, sb + from);
+    bsrc[hi + c] = from;
+}
+
 // restart_terminal_envs, batched.rs:185-203 (and BatchedMCTS::new when force_all)
 template <int N>
 __global__ __launch_bounds__(64) void restart_kernel(SearchDev s, const int32_t* choice, int8_t* terminal_out, int force_all,
@@ -1361,6 +1489,25 @@ int tz_tree_select_best(const SearchDev& s, uint16_t* out_dev, hipStream_t st) {
 }
 int tz_tree_step(const SearchDev& s, const uint16_t* actions_dev, hipStream_t st) {
     TZ_DISPATCH_N(s.n, (step_kernel<NB><<<s.batch, 64, 0, st>>>(s, actions_dev)));
+    TZ_LAUNCH_CHECK();
+    return TZ_OK;
+}
+int tz_tree_step_wide_roots(const SearchDev& s, const uint16_t* actions_dev, uint32_t* status_dev, hipStream_t st) {
+    TZ_DISPATCH_N(s.n, (step_wide_root_kernel<NB><<<s.batch, 64, 0, st>>>(s, actions_dev, status_dev)));
+    TZ_LAUNCH_CHECK();
+    return TZ_OK;
+}
+int tz_tree_step_wide_scan(const SearchDev& s, const StepWideDev& w, int game, uint32_t lo, uint32_t n, hipStream_t st) {
+    const uint32_t nb = (n + TZ_STEP_WIDE_BLOCK - 1) / TZ_STEP_WIDE_BLOCK;
+    step_wide_scan_kernel<<<nb, TZ_STEP_WIDE_BLOCK, 0, st>>>(s, w, game, lo, n);
+    TZ_LAUNCH_CHECK();
+    step_wide_sums_kernel<<<1, TZ_STEP_WIDE_SUMS, 0, st>>>(s, w, game, lo + n, nb);
+    TZ_LAUNCH_CHECK();
+    return TZ_OK;
+}
+int tz_tree_step_wide_copy(const SearchDev& s, const StepWideDev& w, int game, uint32_t lo, uint32_t n, uint32_t total, hipStream_t st) {
+    const uint32_t threads = n > total ? n : total;
+    step_wide_copy_kernel<<<(threads + 255) / 256, 256, 0, st>>>(s, w, game, lo, n, total);
     TZ_LAUNCH_CHECK();
     return TZ_OK;
 }
