@@ -219,6 +219,9 @@ int tz_net_rnd_raw(tz_net* net, int batch, const tz_state* states, float* raw_ou
 int tz_net_hash_indices(tz_net* net, int batch, const tz_state* states, uint32_t* indices_out, int update);
 int tz_net_load_bitset(tz_net* net, const char* path);
 int tz_net_save_bitset(tz_net* net, const char* path);
+/* HashNetwork::forward_hash for host states: seen_out[i] = 1 if position i's index is in the set, 0 if not; the set is not updated
+ * (tz_search_hash_seen is the same on a search handle's positions).  TZ_EINVAL unless the net is a loaded hash net. */
+int tz_net_hash_seen(tz_net* net, int batch, const tz_state* states, uint8_t* seen_out);
 
 /* ---------- BatchedMCTS (search/node/batched.rs:32-409) ---------- */
 /* BatchedMCTS::from_envs with default (empty-board) envs; node_capacity = node slots per game
@@ -357,6 +360,28 @@ int tz_search_terminal_details(tz_search* s, int8_t* reason_out, uint8_t* winner
  * squares' worth, in move order) are recognised: such a move is applied; for any other move, legal or not, ok_out[g] is 0, the
  * position is unchanged and the call returns TZ_ECAPACITY "more legal moves than max_actions" after handling the other games. */
 int tz_search_play_moves(tz_search* s, const uint16_t* actions, int8_t* ok_out);
+/* `steps` uniformly random legal moves for every game of the handle, from its current positions
+ * (Environment::new_opening_with_random_steps after the opening, env.rs:81-95; eee/src/utils.rs reference_envs), in one launch.
+ * The move of game g at a position is row[j] of its legal moves in move order, with
+ *     u = mix64(mix64(mix64(seed) ^ (game_base + g)) ^ ply),   j = ((u >> 32) * n) >> 32,
+ * mix64 = splitmix64's finaliser, ply = the position's own ply counter, n = the number of legal moves: integer arithmetic only,
+ * and a playout made in two calls is the playout made in one.  A game stops before `steps` moves when it has no legal move
+ * (env.rs:89-91), or, with TZ_RANDOM_STOP_AT_TERMINAL, when its position is terminal.  Without that flag the end of a game is not
+ * looked at, as in the reference: random moves go on over a finished game for as long as there are any.
+ * moves_out[g][i] / nlegal_out[g][i]: move i of game g and the number of legal moves it was drawn from; 0xFFFF / 0 from
+ * played_out[g] on.  Any of the three may be NULL.  The trees of all games are reset (also of a game that played nothing); the
+ * captured simulation graphs stay valid, as after tz_search_play_moves.
+ * steps == 0 is valid and changes nothing.  TZ_EINVAL: steps < 0, unknown flag bits, a null handle.  A position with more than 1024
+ * legal moves (6x6 only) ends its game's playout there, the position before that ply kept; the other games finish theirs and the
+ * call returns TZ_ECAPACITY "more legal moves than max_actions".  A later call works again. */
+#define TZ_RANDOM_STOP_AT_TERMINAL 1
+int tz_search_random_steps(tz_search* s, uint64_t seed, uint64_t game_base, int steps, int flags,
+                           uint16_t* moves_out /*[batch][steps] or NULL*/, uint16_t* nlegal_out /*[batch][steps] or NULL*/,
+                           int32_t* played_out /*[batch] or NULL*/);
+/* HashNetwork::forward_hash (net4_lcghash.rs:251-264) on the handle's current positions, without an upload: seen_out[g] = 1 if
+ * the position's index is in the set (the reference's 0.0), 0 if not (MAXIMUM_VARIANCE).  The set is not updated.  TZ_EINVAL
+ * unless the handle's agent is a loaded hash net (net4_simhash, net6_simhash, net4_lcghash). */
+int tz_search_hash_seen(tz_search* s, uint8_t* seen_out /*[batch]*/);
 /* BatchedMCTS::gumbel_sequential_halving with caller-supplied Gumbel(0,1) samples
  * (batched.rs:207-409): gumbel[batch][amax]; selected_out[batch] move indices. */
 int tz_search_gumbel_sh(tz_search* s, const float* betas, int sampled_actions, int search_budget,

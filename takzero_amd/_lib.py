@@ -49,6 +49,7 @@ SYMBOLS = [
     "tz_search_step_wide",
     "tz_tei_create", "tz_tei_destroy", "tz_tei_line", "tz_tei_stop", "tz_tei_set_sink", "tz_tei_set_info_interval", "tz_tei_parse",
     "tz_tei_format_info",
+    "tz_search_random_steps", "tz_search_hash_seen", "tz_net_hash_seen",
 ]
 
 _lib = None
@@ -150,6 +151,9 @@ def load():
                                       C.POINTER(C.c_uint64)]
     lib.tz_search_terminal_details.argtypes = [vp, vp, vp]
     lib.tz_search_play_moves.argtypes = [vp, vp, vp]
+    lib.tz_search_random_steps.argtypes = [vp, C.c_uint64, C.c_uint64, ci, ci, vp, vp, vp]
+    lib.tz_search_hash_seen.argtypes = [vp, vp]
+    lib.tz_net_hash_seen.argtypes = [vp, ci, vp, vp]
     lib.tz_device_math.argtypes = [ci, vp, vp, vp, ci]
     lib.tz_debug_conv_bench.argtypes = [vp, ci, ci, ci, C.POINTER(C.c_float)]
     lib.tz_debug_tower_bench.argtypes = [vp, ci, ci, ci, C.POINTER(C.c_float)]

@@ -34,6 +34,8 @@ EVAL_VALUE, EVAL_WIN, EVAL_LOSS, EVAL_DRAW = 0, 1, 2, 3
 SELECT_PUCT, SELECT_UCT, SELECT_IMPROVED = 0, 1, 2
 SELECT_NAMES = {"puct": SELECT_PUCT, "uct": SELECT_UCT, "improved": SELECT_IMPROVED}
 TERMINAL_NONE, TERMINAL_WIN, TERMINAL_LOSS, TERMINAL_DRAW = -1, 0, 1, 2
+RANDOM_STOP_AT_TERMINAL = 1   # tz_search_random_steps flag
+MAXIMUM_VARIANCE = 4.0        # what HashNetwork::forward_hash returns for an unseen position (net4_lcghash.rs:27)
 DISCOUNT_FACTOR = np.float32(0.997)  # search/mod.rs:7
 
 
@@ -224,6 +226,17 @@ class Net:
         out = np.zeros(len(st), np.uint32)
         check(self.lib.tz_net_hash_indices(self.h, len(st), st.ctypes.data, out.ctypes.data, 1 if update else 0))
         return out
+
+    def hash_seen(self, env_batch):
+        """uint8[B]: 1 where the position's index is in the set; the set is not updated (tz_net_hash_seen)."""
+        st = _states(env_batch)
+        out = np.zeros(len(st), np.uint8)
+        check(self.lib.tz_net_hash_seen(self.h, len(st), st.ctypes.data, out.ctypes.data))
+        return out
+
+    def forward_hash(self, env_batch):
+        """HashNetwork::forward_hash (net4_lcghash.rs:251-264) as the reference returns it: float32[B], 0.0 seen, 4.0 unseen."""
+        return np.where(self.hash_seen(env_batch) != 0, np.float32(0.0), np.float32(MAXIMUM_VARIANCE)).astype(np.float32)
 
     def load_bitset(self, path):
         check(self.lib.tz_net_load_bitset(self.h, str(path).encode()))
@@ -462,6 +475,26 @@ class BatchedMCTS:
         ok = np.zeros(self.batch, np.int8)
         check(self.lib.tz_search_play_moves(self.h, a.ctypes.data, ok.ctypes.data))
         return ok
+
+    def random_steps(self, steps, seed, game_base=0, stop_at_terminal=False):
+        """`steps` uniformly random legal moves for every game, from its current position, in one launch
+        (Environment::new_opening_with_random_steps after the opening, env.rs:81-95).  Game g's draws are keyed by
+        (seed, game_base + g, the position's ply): see tz_search_random_steps.  Returns (moves[B, steps] uint16, 0xFFFF past the
+        end; nlegal[B, steps] uint16, the width each move was drawn from; played[B] int32).  Trees are reset."""
+        steps = int(steps)
+        moves = np.full((self.batch, max(steps, 0)), 0xFFFF, np.uint16)
+        nlegal = np.zeros((self.batch, max(steps, 0)), np.uint16)
+        played = np.zeros(self.batch, np.int32)
+        check(self.lib.tz_search_random_steps(self.h, int(seed) & (2**64 - 1), int(game_base) & (2**64 - 1), steps,
+                                              RANDOM_STOP_AT_TERMINAL if stop_at_terminal else 0,
+                                              moves.ctypes.data, nlegal.ctypes.data, played.ctypes.data))
+        return moves, nlegal, played
+
+    def hash_seen(self):
+        """HashNetwork::forward_hash on the handle's current positions, no upload: uint8[B], 1 = the index is in the set."""
+        out = np.zeros(self.batch, np.uint8)
+        check(self.lib.tz_search_hash_seen(self.h, out.ctypes.data))
+        return out
 
     def counters(self):
         a, b = C.c_uint64(), C.c_uint64()

@@ -837,6 +837,41 @@ int tz_search_play_moves(tz_search* s, const uint16_t* actions, int8_t* ok_out) 
     return check_error_flag(s);  // synchronises; flag 3: a move could not be judged (see the header)
 }
 
+int tz_search_random_steps(tz_search* s, uint64_t seed, uint64_t game_base, int steps, int flags, uint16_t* moves_out,
+                           uint16_t* nlegal_out, int32_t* played_out) {
+    if (!s) return tz_fail(TZ_EINVAL, "tz_search_random_steps: null handle");
+    if (steps < 0) return tz_fail(TZ_EINVAL, "tz_search_random_steps: negative steps");
+    if (flags & ~TZ_RANDOM_STOP_AT_TERMINAL) return tz_fail(TZ_EINVAL, "tz_search_random_steps: unknown flag bits");
+    const size_t B = (size_t)s->d.batch;
+    if (steps == 0) {
+        if (played_out) memset(played_out, 0, B * sizeof(int32_t));
+        return TZ_OK;
+    }
+    TZ_HIP(hipSetDevice(s->device));
+    // staging: moves [B][steps] u16, legal counts [B][steps] u16, played [B] i32
+    const size_t row = B * (size_t)steps * sizeof(uint16_t);
+    int rc = ensure_child(s, 2 * row + B * sizeof(int32_t));
+    if (rc) return rc;
+    uint16_t* moves_dev = (uint16_t*)s->child_dev;
+    uint16_t* nlegal_dev = (uint16_t*)((char*)s->child_dev + row);
+    int32_t* played_dev = (int32_t*)((char*)s->child_dev + 2 * row);
+    if ((rc = tz_tree_random_steps(s->d, seed, game_base, steps, (flags & TZ_RANDOM_STOP_AT_TERMINAL) != 0, moves_dev, nlegal_dev, played_dev,
+                                   s->stream)))
+        return rc;
+    if (moves_out) TZ_HIP(hipMemcpyAsync(moves_out, moves_dev, row, hipMemcpyDeviceToHost, s->stream));
+    if (nlegal_out) TZ_HIP(hipMemcpyAsync(nlegal_out, nlegal_dev, row, hipMemcpyDeviceToHost, s->stream));
+    if (played_out) TZ_HIP(hipMemcpyAsync(played_out, played_dev, B * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+    return check_error_flag(s);  // synchronises; flag 3: a game met a position wider than the row (see the header)
+}
+
+int tz_search_hash_seen(tz_search* s, uint8_t* seen_out) {
+    if (!s || !seen_out) return tz_fail(TZ_EINVAL, "tz_search_hash_seen: null argument");
+    if (!s->net || !s->net->has_hash || !s->net->loaded)
+        return tz_fail(TZ_EINVAL, "tz_search_hash_seen: the handle's agent is not a loaded hash network");
+    TZ_HIP(hipSetDevice(s->device));
+    return tz_net_hash_seen_device(s->net, s->d.env, s->d.batch, seen_out, s->stream);
+}
+
 int tz_search_gumbel_sh(tz_search* s, const float* betas, int sampled_actions, int search_budget, const float* gumbel,
                         int amax, uint16_t* selected_out) {
     if (!s || !betas || !gumbel || !selected_out || sampled_actions <= 0 || amax <= 0)

@@ -125,3 +125,5 @@ int tz_tree_descend_batch(const SearchDev& s, const LeafBatchDev& b, hipStream_t
 int tz_tree_compact_batch(const SearchDev& s, const LeafBatchDev& b, hipStream_t st);
 int tz_tree_expand_batch(const SearchDev& s, const LeafBatchDev& b, const NetOut& out, hipStream_t st);
 int tz_tree_play_moves(const SearchDev& s, const uint16_t* actions_dev, int8_t* ok_dev, hipStream_t st);
+int tz_tree_random_steps(const SearchDev& s, uint64_t seed, uint64_t game_base, int steps, bool stop_at_terminal, uint16_t* moves_dev,
+                         uint16_t* nlegal_dev, int32_t* played_dev, hipStream_t st);

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "tz_engine.h"
+#include "tz_math.h"
 #include "tz_ot.h"
 
 extern "C" int tz_trainer_snapshot(tz_trainer* t, TensorStore& out);   // tz_learn.hip
@@ -218,13 +219,8 @@ int rnd_calibrate(tz_learn* l) {
                                     nullptr, nullptr);
 }
 
-// the project's counter-based draws (as Net::new's initialisers): a 64-bit finaliser over the key
-uint64_t mix64(uint64_t x) {
-    x += 0x9e3779b97f4a7c15ull;
-    x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
-    x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
+// the project's counter-based draws (as Net::new's initialisers): a 64-bit finaliser over the key (tz_math.h)
+uint64_t mix64(uint64_t x) { return tz_mix64(x); }
 
 int step_batch(tz_learn* l, int slot, int train_ube, float* losses) {
     auto& T = l->tensors[slot];

@@ -135,6 +135,15 @@ TZ_HD float tz_powif(float a, int b) {
     return b < 0 ? 1.0f / mul : mul;
 }
 
+// The project's counter-based draws (Net::new's initialisers, the learn loop's pre-training moves, the random playouts of
+// tz_search_random_steps): splitmix64's finaliser over a key.  Integer only, so host and device agree bit for bit.
+TZ_HD uint64_t tz_mix64(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
 #define TZ_DISCOUNT 0.997f  // search/mod.rs:7
 
 #endif  // TZ_MATH_H

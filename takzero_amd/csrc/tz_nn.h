@@ -86,4 +86,7 @@ void tz_net_invalidate_captures(tz_net* net);
 // If count_dev is non-null the number of valid slots is read on the device (<= max_positions).
 int tz_net_forward_device(tz_net* net, const tz_state* states_dev, const int32_t* game_index_dev,
                           const int32_t* count_dev, int count_host, int max_positions, hipStream_t st, NetOut* out);
+// HashNetwork::forward_hash on `batch` positions already on the device: seen_host[i] = 1 if position i's index is in the set.  The
+// set is not updated.  Synchronises `st`.
+int tz_net_hash_seen_device(tz_net* net, const tz_state* states_dev, int batch, uint8_t* seen_host, hipStream_t st);
 int tz_nn_encode_planes(int n, int cin, const tz_state* states_dev, int count, float* planes_dev, hipStream_t st);

@@ -2895,6 +2895,12 @@ __global__ void bitset_set_kernel(uint32_t* bitset, const uint32_t* index, int n
     if (i < n) atomicOr(&bitset[index[i] >> 5], 1u << (index[i] & 31));
 }
 
+// HashNetwork::forward_hash (net4_lcghash.rs:251-264): membership of every index, nothing set
+__global__ void bitset_lookup_kernel(const uint32_t* bitset, const uint32_t* index, int n, uint8_t* seen) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) seen[i] = (uint8_t)((bitset[index[i] >> 5] >> (index[i] & 31)) & 1u);
+}
+
 // logits of the legal actions: out[b][j] = policy[b][px(a)][ch(a)]  (net5.rs:239-267)
 __global__ void gather_kernel(const float* policy, int nn, int stride, const uint16_t* legal, const int32_t* cnt,
                               int amax, int batch, float* out) {
@@ -4185,6 +4191,27 @@ int tz_net_forward_device(tz_net* net, const tz_state* states, const int32_t* gi
     return TZ_OK;
 }
 
+int tz_net_hash_seen_device(tz_net* net, const tz_state* states_dev, int batch, uint8_t* seen_host, hipStream_t st) {
+    int rc = tz_net_ensure_batch(net, batch);   // launch_hash_state writes `local` of every position into net->aux
+    if (rc) return rc;
+    void* scratch = nullptr;   // [batch] indices, then [batch] flags
+    TZ_HIP(hipMalloc(&scratch, (size_t)batch * 5));
+    uint32_t* didx = (uint32_t*)scratch;
+    uint8_t* dseen = (uint8_t*)scratch + (size_t)batch * 4;
+    hipError_t e = hipSuccess;
+    rc = launch_hash_state(net, states_dev, nullptr, nullptr, batch, batch, didx, st);
+    if (!rc) {
+        bitset_lookup_kernel<<<(batch + 255) / 256, 256, 0, st>>>(net->bitset, didx, batch, dseen);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(seen_host, dseen, batch, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    }
+    (void)hipFree(scratch);
+    if (rc) return rc;
+    if (e != hipSuccess) return tz_fail(TZ_EDEVICE, std::string("hash_seen: ") + hipGetErrorString(e));
+    return TZ_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 extern "C" {
 
@@ -4494,12 +4521,7 @@ int tz_net_tensor_info(tz_net* net, int i, char* name_out, int name_cap, uint64_
 // statistics 0 / 1, RND min 0 / max 1 (net5.rs:166-168), simhash_matrix N(0,1), lcghash_init U(-100, 100).  The draws come from a counter-based
 // generator keyed by (seed, tensor name): tch's own stream (torch's Philox/mt19937 through manual_seed) is not reproduced.
 namespace {
-uint64_t mix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
+uint64_t mix64(uint64_t x) { return tz_mix64(x); }   // tz_math.h
 struct InitRng {
     uint64_t key, ctr = 0;
     InitRng(uint64_t seed, const std::string& name) : key(mix64(seed)) {
@@ -5069,6 +5091,18 @@ int tz_net_hash_indices(tz_net* net, int batch, const tz_state* states, uint32_t
     if (rc) return rc;
     if (e != hipSuccess) return tz_fail(TZ_EDEVICE, std::string("tz_net_hash_indices: ") + hipGetErrorString(e));
     return TZ_OK;
+}
+
+// HashNetwork::forward_hash for host states: 1 where the reference returns 0.0 (seen), 0 where it returns MAXIMUM_VARIANCE
+int tz_net_hash_seen(tz_net* net, int batch, const tz_state* states, uint8_t* seen_out) {
+    if (!net || !states || !seen_out || batch <= 0) return tz_fail(TZ_EINVAL, "tz_net_hash_seen: bad argument");
+    if (!net->has_hash || !net->loaded) return tz_fail(TZ_EINVAL, "tz_net_hash_seen: not a loaded hash network");
+    tz_state* dstates = nullptr;
+    int rc = net_upload_states(net, batch, states, &dstates);
+    if (rc) return rc;
+    rc = tz_net_hash_seen_device(net, dstates, batch, seen_out, net->stream);
+    (void)hipFree(dstates);
+    return rc;
 }
 
 // Diagnostic: the hash net's index-plus-lookup kernel alone, timed between two events (tools/lcghash_rate.py)

@@ -1331,6 +1331,68 @@ __global__ __launch_bounds__(64) void play_moves_kernel(SearchDev s, const uint1
     }
 }
 
+// a wave-uniform 64-bit value held in scalar registers
+__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// Uniformly random legal play (Environment::new_opening_with_random_steps after the opening, env.rs:81-95): up to `steps` plies per
+// game in one launch, the position in LDS throughout.  The draw of a ply is keyed by (seed, game, the position's own ply), so a
+// playout made in two calls is the playout made in one.  key = tz_mix64(seed).  A game stops early when it has no legal move
+// (env.rs:89-91), when its move list is wider than the row (flag 3, the position before that ply stays), or, with
+// TZ_RANDOM_STOP_AT_TERMINAL, when it is over; without that flag terminal() is never asked, as in the reference.  Trees are reset.
+// moves_out / nlegal_out are [batch][steps], 0xFFFF / 0 past played_out[g].
+template <int N>
+__global__ __launch_bounds__(64) void random_steps_kernel(SearchDev s, uint64_t key, uint64_t game_base, int steps, int stop_at_terminal,
+                                                          uint16_t* moves_out, uint16_t* nlegal_out, int32_t* played_out) {
+    constexpr int NN = N * N;
+    const int g = blockIdx.x, l = lane_id();
+    __shared__ tz_state env;
+    __shared__ uint8_t reach[NN * 4];
+    __shared__ uint16_t acts[1024];
+    load_state(&env, &s.env[g]);
+    __syncthreads();
+    const uint64_t game_key = tz_mix64(key ^ (game_base + (uint64_t)g));   // blockIdx and kernel arguments: scalar
+    uint16_t* mv = moves_out + (size_t)g * steps;
+    uint16_t* nl = nlegal_out + (size_t)g * steps;
+    int played = 0;
+    for (; played < steps; played++) {
+        if (stop_at_terminal && terminal<N>(&env) != TZ_TERMINAL_NONE) break;
+        const int n = __builtin_amdgcn_readfirstlane(gen_moves<N>(&env, reach, acts, 1024));
+        if (n == 0) break;
+        if (n > 1024) {   // gen_moves cannot hand out the moves past the row
+            if (l == 0) atomicMax(s.error_flag, 3);
+            break;
+        }
+        const uint64_t ply = uniform64((uint64_t)env.ply);
+        const uint64_t u = tz_mix64(game_key ^ ply);
+        const int j = (int)(((u >> 32) * (uint64_t)n) >> 32);   // < n: (u >> 32) < 2^32
+        const int a = __builtin_amdgcn_readfirstlane((int)acts[j]);
+        if (l == 0) {
+            mv[played] = (uint16_t)a;
+            nl[played] = (uint16_t)n;
+        }
+        apply_move<N>(&env, a);
+        __syncthreads();
+    }
+    for (int i = played + l; i < steps; i += 64) {
+        mv[i] = 0xFFFF;
+        nl[i] = 0;
+    }
+    {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(&env);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(&s.env[g]);
+        for (int i = l; i < (int)(sizeof(tz_state) / 4); i += 64) dst[i] = src[i];
+    }
+    if (l == 0) {
+        played_out[g] = played;
+        write_default_node(s, slab_base(s, s.bank[g], g));
+        s.alloc[g] = 1;
+    }
+}
+
 __global__ void reset_games_kernel(SearchDev s, const int32_t* idx, int count) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
@@ -1520,6 +1582,14 @@ int tz_tree_restart(const SearchDev& s, const int32_t* choice_dev, int8_t* termi
 }
 int tz_tree_play_moves(const SearchDev& s, const uint16_t* actions_dev, int8_t* ok_dev, hipStream_t st) {
     TZ_DISPATCH_N(s.n, (play_moves_kernel<NB><<<s.batch, 64, 0, st>>>(s, actions_dev, ok_dev)));
+    TZ_LAUNCH_CHECK();
+    return TZ_OK;
+}
+int tz_tree_random_steps(const SearchDev& s, uint64_t seed, uint64_t game_base, int steps, bool stop_at_terminal, uint16_t* moves_dev,
+                         uint16_t* nlegal_dev, int32_t* played_dev, hipStream_t st) {
+    const uint64_t key = tz_mix64(seed);
+    TZ_DISPATCH_N(s.n, (random_steps_kernel<NB><<<s.batch, 64, 0, st>>>(s, key, game_base, steps, stop_at_terminal ? 1 : 0, moves_dev,
+                                                                        nlegal_dev, played_dev)));
     TZ_LAUNCH_CHECK();
     return TZ_OK;
 }
